@@ -29,6 +29,17 @@ rank processes itself before anything touches a GPU (torchrun's environment per 
 127.0.0.1), relays rank 0's JSON line and exits with the worst rank's status. It refuses (exit 2) a
 `--gpus` that disagrees with WORLD_SIZE or exceeds the visible GPUs (the gloo rehearsal excepted).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs and no more: set up,
+W warm-up steps, the N timed steps, the outputs if `--dump-outputs DIR` asks for them, the JSON line
+(`value`, `ms_per_step`, the grouped step's tokens/s). Every other section — roofline, decode_chain,
+persistent_chain, multi_gpu_throughput, the headline / n1 / batched / next_rows shapes, multi_gpu_world1,
+host_path_pcie, cpu_baseline — takes runs of its own and is behind `--full`; there each `--no-*` switch
+drops its section as before.
+
+`--dump-outputs DIR` writes what the last timed step left in the output buffer, the dst vector of every
+MUL_MAT node, as DIR/<matrix>.npy (float32 [layers, M]; q, k, v, o, gate, up, down). Operands are seeded,
+so two builds run with the same arguments can be compared output for output.
+
 Exit status: the JSON line is always printed; the run exits 3 afterwards when any section reports
 an error or any bounded in-launch wait gave up (sync_wait_timeouts), so a driver never takes a
 partial line for a clean one.
@@ -60,6 +71,7 @@ NEXT_X = {"h": "down", "attn": "o", "h2": "v", "ffn": "up"}
 CHAIN = [("q", "k", "v"), ("o",), ("gate", "up"), ("down",)]
 Q4_0_BLOCK = 18
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def alg_bytes(M, K, N=1):
@@ -127,6 +139,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--layers", type=int, default=LAYERS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other section too (roofline, decode chain, other shapes, "
+                         "host path, CPU baseline); the --no-* switches below drop single sections of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<matrix>.npy (float32 [layers, M])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-headline", action="store_true")
     ap.add_argument("--no-chain", action="store_true")
@@ -139,6 +156,9 @@ def main():
     ap.add_argument("--sharded", action="store_true",
                     help="the N > 1 path (C-ABI RCCL communicator + lk_sharded_plan) at any world size")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps alone
+        args.no_cpu_baseline = args.no_headline = args.no_chain = args.no_batched = True
+        args.no_host_path = args.no_multi_gpu_cost = args.no_throughput = True
 
     import torch
     import torch.distributed as dist
@@ -304,8 +324,10 @@ def main():
     tokens = args.steps
     value_gbs = token_bytes * tokens / elapsed / 1e9
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:  # before any other section launches on these nodes
+        dump_outputs(args.dump_outputs, obuf_u8, nodes_by_layer)
 
-    roof = roofline(torch, local_plans, local_by_layer, compute, world)
+    roof = roofline(torch, local_plans, local_by_layer, compute, world) if args.full else None
 
     # the decode figure: the dependent order {q,k,v} -> o -> {gate,up} -> down (4 launches per layer;
     # at N > 1 each a sharded plan with its all-gather), timed on every rank, max over ranks
@@ -353,8 +375,9 @@ def main():
                    "launches_per_step_per_rank": launches_per_step, "hip_graph": graph is not None,
                    "ranks_seen_by_rccl": comm.rcclRanks if comm is not None else None,
                    "gpu_ms_per_step": round(ev_ms / args.steps, 4)},
-        "roofline": roof,
     }
+    if roof is not None:
+        result["roofline"] = roof
 
     # the failure contract: a bounded in-launch wait that gave up is counted per
     # section and reported here (lk_sync_timeouts also clears the flag the next synchronous entry
@@ -416,6 +439,19 @@ def main():
     if failed:
         print(f"[bench] failed sections: {failed}", file=sys.stderr)
         sys.exit(3)
+
+
+def dump_outputs(path, obuf_u8, nodes_by_layer):
+    """What a caller of the timed step receives: every node's dst vector as the last step left it in
+    the output buffer, per matrix name as path/<name>.npy, float32 [layers, M] (5.4 MB at 32 layers;
+    the first DUMP_MAX_BYTES worth of layers should --layers ask for more)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = obuf_u8.cpu().numpy()
+    keep = nodes_by_layer[:max(1, DUMP_MAX_BYTES // (4 * sum(M for (_, M, _) in LAYER_MATS)))]
+    for (name, M, _) in LAYER_MATS:
+        offs = [n[name][2].dataOffset for n in keep]
+        np.save(os.path.join(path, name + ".npy"), np.stack([host[o:o + 4 * M].view(np.float32) for o in offs]))
 
 
 def roofline(torch, plans, local_by_layer, stream, world, reps=10):

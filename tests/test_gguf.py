@@ -5,7 +5,8 @@ through the Python mirror ggml_hip.gguf, checked against
     (src/nativeTest/kotlin/ai/solace/llamakotlin/gguf/) over TestGGUFGenerator's file,
     which oracle/gguf_oracle.reference_test_file() reproduces byte for byte;
   * the GGUF files the reference ships (models/ggml-vocab-*.gguf, real llama.cpp output),
-    parsed by the oracle restatement, when /root/reference is present;
+    parsed by the oracle restatement — stored under tests/golden/gguf/, the ones over 1 MiB
+    with their arrays cut to the first 2048 elements (tests/golden/make_gguf_vocab.py);
   * the oracle on synthetic files with every value type and the quantized tensor types,
     and on truncated/corrupted images (same error class, or both succeed identically).
 """
@@ -18,7 +19,8 @@ import pytest
 
 import gguf_oracle as GO
 
-REF_MODELS = "/root/reference/models"
+VOCAB_FILES = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gguf", "*.gguf")))
+assert len(VOCAB_FILES) == 12, "tests/golden/gguf/ is part of the suite"
 
 
 def _parse(data, kotlin_ids=False):
@@ -174,11 +176,9 @@ def _assert_same(mine, ref):
     assert mine["tensors"] == ref["tensors"]
 
 
-@pytest.mark.skipif(not glob.glob(os.path.join(REF_MODELS, "*.gguf")), reason="reference models/ absent")
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(REF_MODELS, "*.gguf"))),
-                         ids=lambda p: os.path.basename(p))
+@pytest.mark.parametrize("path", VOCAB_FILES, ids=lambda p: os.path.basename(p))
 def test_reference_vocab_files(path):
-    """Real llama.cpp GGUF v3 files shipped with the reference: every key, type and value."""
+    """Real llama.cpp GGUF v3 files shipped with the reference (tests/golden/gguf/): every key, type and value."""
     from ggml_hip.gguf import ModelLoader
     data = open(path, "rb").read()
     m = ModelLoader().loadFromFile(path)

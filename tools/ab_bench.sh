@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
   for set in $SETS; do
     envs=()
     [ "$set" = - ] || IFS=, read -ra envs <<< "$set"
-    env "${envs[@]}" timeout -k 10 300 python bench.py --no-batched --no-host-path --no-cpu-baseline --no-multi-gpu-cost "$@" \
+    env "${envs[@]}" timeout -k 10 300 python bench.py --full --no-batched --no-host-path --no-cpu-baseline --no-multi-gpu-cost "$@" \
       > gpurun_out/ab_bench_run.log 2> gpurun_out/ab_bench_err.log
     rc=$?
     if [ $rc -ne 0 ]; then echo "bench rc=$rc ($set)"; tail -5 gpurun_out/ab_bench_err.log; exit $rc; fi

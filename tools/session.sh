@@ -29,6 +29,7 @@ if [ -n "$BENCH" ]; then
   fi
 fi
 if [ -n "$PMC" ]; then
+  : "${PMC_CMD:=python3 bench.py --full --steps 3 --warmup 1}"  # counters over every section's kernels
   IFS='|' read -r -a SETS <<< "$PMC"
   i=0
   for c in "${SETS[@]}"; do
