@@ -31,6 +31,9 @@
  *                         is single-device; this is the north star's row sharding).
  *   lk_graph_*            core/GGMLComputeOps.kt:2515-2652 computeGraph/computeMulMat over
  *                         host buffers with activations kept in HBM between nodes.
+ *   lk_binary/unary_device, lk_mul_mat_gated_device, lk_plan_create_gated, lk_graph_create_ops
+ *                         core/GGMLComputeOps.kt:735 computeAdd, :811 computeMul, :1581 computeGelu,
+ *                         :2633 computeSilu (F32) and the MLP's gated product over them.
  *   lk_weights_pin/evict  residency cache behind GGMLBackendBuffer.setTensor
  *                         (core/GGMLBackend.kt:63-69) for host-authoritative ByteArrays.
  *   lk_dequantize_device  core/GGMLComputeOps.kt:918 dequantizeTensor (Q8_0/Q4_0/Q4_1).
@@ -240,6 +243,41 @@ int lk_debug_poke_gemm_counter(void *stream, int64_t index, int32_t value);
 int lk_scratch_release(void *stream);
 uint64_t lk_scratch_bytes(void);
 
+/* ---- F32 element-wise ops and the gated product (the Llama MLP's glue) --------------------
+ * computeAdd / computeMul / computeGelu (core/GGMLComputeOps.kt:735-759, :811 ff., :1581-1594)
+ * over device buffers, element by element in the Kotlin order with separate roundings:
+ *   LK_BINARY_ADD  a + b                      LK_BINARY_MUL  a · b
+ *   LK_ACT_GELU    (x·0.5f) · (1.0f + tanhf(0.797885f · (x + ((0.044715f·x)·x)·x)))
+ *   LK_ACT_SILU    x / (1.0f + expf(−x)) — explicit API only: the reference's computeSilu
+ *                  (:2633-2638) computes GELU, so a GGMLOp.SILU graph node is LK_ACT_GELU.
+ * Checks in Kotlin's order: a.ne != b.ne or a.ne != dst.ne in any of the 4 dimensions, dst.type !=
+ * a.type: LK_ERR_INVALID_ARG; a type other than F32: LK_ERR_NOT_IMPLEMENTED (CPU path). Empty
+ * tensors: LK_OK, nothing done. Missing buffer: LK_ERR_NO_BUFFER; an element past its buffer:
+ * LK_ERR_OUT_OF_BOUNDS. Every tensor's own nb is honoured in all four dimensions (getFloat(*indices));
+ * a base or stride not a multiple of 4: LK_ERR_NOT_IMPLEMENTED. dst may be exactly a or exactly b
+ * (same base, same strides: an in-place residual); any other overlap: LK_ERR_NOT_IMPLEMENTED.
+ * Stream-ordered and graph-capturable like lk_mul_mat_device. */
+enum lk_binary_op { LK_BINARY_ADD = 1, LK_BINARY_MUL = 2 };
+enum lk_act { LK_ACT_NONE = 0, LK_ACT_GELU = 1, LK_ACT_SILU = 2 };
+int lk_binary_device(int32_t op, const lk_tensor *a, const lk_tensor *b, lk_tensor *dst, void *stream);
+int lk_unary_device(int32_t act, const lk_tensor *a, lk_tensor *dst, void *stream);
+/* dst = A · (act(gate) ⊙ up): computeGelu(gate) -> t, computeMul(t, up) -> h, computeMatMul(a, h, dst),
+ * checked in that order, without t and h reaching memory when A streams: gate and up are F32 [N, K],
+ * a any type lk_mul_mat_device takes against an F32 b, act != LK_ACT_NONE (LK_ERR_INVALID_ARG).
+ * Where the plain product would run the streaming GEMV and gate and up are contiguous and 16-byte
+ * aligned, the kernel builds its activation image from both (route stream_gated<qt,cpl>); every
+ * other case writes h into the per-(device, stream) scratch with one element-wise launch and runs
+ * the ordinary route on it. Same bits as the three calls either way. */
+int lk_mul_mat_gated_device(const lk_tensor *a, const lk_tensor *gate, const lk_tensor *up, int32_t act,
+                            lk_tensor *dst, void *stream);
+/* lk_plan_create (stage == NULL) or lk_plan_create_chain (stage != NULL) over nodes that may be
+ * gated: act[i] == LK_ACT_NONE is a plain node (up[i] ignored), otherwise node i computes
+ * a[i] · (act[i](b[i]) ⊙ up[i]) with b[i] the gate. In a chain a gated node of stage s may read gate
+ * and up that stage s − 1 produced (the same barrier, write-through outputs and sc1 loads); a gated
+ * chain node that cannot stream returns LK_ERR_NOT_IMPLEMENTED like any other. */
+int lk_plan_create_gated(const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const int32_t *act,
+                         const lk_tensor *dst, const int32_t *stage, int n, lk_plan **out);
+
 /* ---- multi-GPU: row shards + RCCL all-gather over xGMI -----------------
  * The reference is single-device; this is the north star's partition of the same operator.
  * Rank r of P owns rows [r·M/P, (r+1)·M/P) of every weight matrix (contiguous bytes: rows are
@@ -368,6 +406,20 @@ void lk_p2p_chain_destroy(lk_p2p_chain *chain);
 typedef struct lk_graph lk_graph;
 int lk_graph_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n,
                     const uint8_t *outputs, uint64_t weight_generation, lk_graph **out);
+/* The same over a graph that also holds F32 element-wise nodes (computeGraph's switch,
+ * core/GGMLComputeOps.kt:2528-2550). op[i] is the node's GGMLOp ordinal (core/GGMLTypes.kt:175 ff.):
+ *   LK_OP_ADD = 2, LK_OP_MUL = 5, LK_OP_GELU = 19, LK_OP_SILU = 21 (computed as GELU, like the
+ *   reference), LK_OP_MUL_MAT = 26; any other value: LK_ERR_NOT_IMPLEMENTED.
+ * a[i], b[i] are the node's src[0], src[1] (b[i] ignored for GELU / SILU), dst[i] the node. Levels come
+ * from byte ranges as for lk_graph_create; a level's element-wise nodes are launched one by one after
+ * its plan. One pass fuses MUL_MAT(W, MUL(ACT(g), u)) (or MUL(u, ACT(g))) into one gated node
+ * (lk_mul_mat_gated_device's arithmetic) when neither intermediate is read or written by any other
+ * node nor marked in outputs: fused intermediates get no device mirror and are never written back. */
+enum lk_op { LK_OP_ADD = 2, LK_OP_MUL = 5, LK_OP_GELU = 19, LK_OP_SILU = 21, LK_OP_MUL_MAT = 26 };
+int lk_graph_create_ops(const int32_t *op, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n,
+                        const uint8_t *outputs, uint64_t weight_generation, lk_graph **out);
+/* Gated nodes the fusion pass made (0 for lk_graph_create's graphs). */
+int lk_graph_num_fused(const lk_graph *g);
 /* The same graph row-sharded over the GPUs of a node (the north star's partition behind the
  * graph API): every quantized weight node whose rows split evenly (M % P == 0, K % 32 == 0, dense
  * F32 dst) runs rank r's rows [r·M/P, (r+1)·M/P) on rank r's device — only that shard of the

@@ -377,6 +377,31 @@ int launch_stream(int32_t qt, int cpl, int grid, const GemvDesc &single, const S
   return fail(LK_ERR_NOT_IMPLEMENTED, "stream gemv: type %d class %d", qt, cpl);
 }
 
+// The gated instantiation (gemv_stream_gated): gates parallels work (plans), or up / act for a
+// single launch.
+template <int QT, int CPL>
+void launch_stream_gated_t(int grid, const GemvDesc &single, const float *up, int act, const StreamWork *work,
+                           const StreamGate *gates, int spw, hipStream_t st) {
+  constexpr size_t lds = StreamGeom<QT, CPL>::LDS;
+  hipLaunchKernelGGL((gemv_stream_gated<QT, CPL>), dim3(grid), dim3(kStreamWaves * 64), lds, st, work, spw, gates, single.a,
+                     single.x, single.dst, single.dst_row_stride, single.M, single.K, up, act);
+}
+
+int launch_stream_gated(int32_t qt, int cpl, int grid, const GemvDesc &single, const float *up, int act,
+                        const StreamWork *work, const StreamGate *gates, int spw, hipStream_t st) {
+  if (grid <= 0) return LK_OK;
+  note_route("stream_gated<%d,%d>:g%d%s", qt, cpl, grid, work ? "p" : "");
+#define LK_STREAM(T, C) \
+  if (qt == T && cpl == C) { launch_stream_gated_t<T, C>(grid, single, up, act, work, gates, spw, st); HIP_TRY(hipGetLastError()); return LK_OK; }
+  LK_STREAM(LK_TYPE_Q4_0, 1) LK_STREAM(LK_TYPE_Q4_0, 2) LK_STREAM(LK_TYPE_Q4_0, 3)
+  LK_STREAM(LK_TYPE_Q4_1, 1) LK_STREAM(LK_TYPE_Q4_1, 2) LK_STREAM(LK_TYPE_Q4_1, 3)
+  LK_STREAM(LK_TYPE_Q8_0, 1) LK_STREAM(LK_TYPE_Q8_0, 2) LK_STREAM(LK_TYPE_Q8_0, 3)
+  LK_STREAM(LK_TYPE_Q4_K, 1) LK_STREAM(LK_TYPE_Q4_K, 2) LK_STREAM(LK_TYPE_Q4_K, 3)
+  LK_STREAM(LK_TYPE_Q2_K, 1) LK_STREAM(LK_TYPE_Q2_K, 2) LK_STREAM(LK_TYPE_Q2_K, 3)
+#undef LK_STREAM
+  return fail(LK_ERR_NOT_IMPLEMENTED, "gated stream gemv: type %d class %d", qt, cpl);
+}
+
 // Workgroups for `rows` rows: one per CU, but no fewer than ~kStreamWaves rows each.
 int stream_grid(int64_t rows) {
   const int64_t g = (rows + kStreamWaves - 1) / kStreamWaves;
@@ -423,6 +448,7 @@ struct GemmScratch {
   int32_t *counter = nullptr; size_t counter_n = 0;
   unsigned *tcnt = nullptr;  // split-K arrival counters, one word per output tile of a launch
   size_t tcnt_n = 0;
+  void *gated = nullptr; size_t gated_bytes = 0;  // h = act(gate) ⊙ up of a composed gated product
   std::vector<void *> retired;
   uint64_t retired_bytes = 0;
   uint64_t epoch = 0;
@@ -1389,6 +1415,170 @@ int mul_mat_device_checked(const lk_tensor *a, const lk_tensor *b, lk_tensor *ds
   return launch_generic(a, b, dst, c, st);
 }
 
+// ---- F32 element-wise ops (computeAdd / computeMul / computeGelu) and the gated product ----------
+
+// Byte footprint [lo, hi) of a 4-D strided F32 tensor (offsets inside its buffer).
+void span4(const lk_tensor *t, uint64_t *lo, uint64_t *hi) {
+  uint64_t last = t->data_offset;
+  for (int i = 0; i < 4; i++) last += (uint64_t)(std::max<int64_t>(t->ne[i], 1) - 1) * t->nb[i];
+  *lo = t->data_offset;
+  *hi = last + 4;
+}
+
+struct EwChecked {
+  int64_t n = 0;      // elements; 0: nothing is read or written
+  uint64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0, d_lo = 0, d_hi = 0;
+};
+
+bool ew_contiguous(const lk_tensor *t) {
+  uint64_t want = 4;
+  for (int i = 0; i < 4; i++) {
+    if (t->ne[i] > 1 && t->nb[i] != want) return false;
+    want *= (uint64_t)std::max<int64_t>(t->ne[i], 1);
+  }
+  return true;
+}
+
+// The checks of computeAdd / computeMul (b != null) or computeGelu (b == null), in Kotlin's order,
+// then what the device path needs (buffers, bounds, 4-byte alignment, no partial overlap).
+int ew_check(const char *what, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, EwChecked *c) {
+  if (!a || !dst) return fail(LK_ERR_INVALID_ARG, "null tensor descriptor");
+  if (b)
+    for (int i = 0; i < 4; i++)
+      if (a->ne[i] != b->ne[i]) return fail(LK_ERR_INVALID_ARG, "Incompatible dimensions for %s", what);
+  for (int i = 0; i < 4; i++)
+    if (a->ne[i] != dst->ne[i]) return fail(LK_ERR_INVALID_ARG, "Result tensor dimensions must match input dimensions");
+  if (dst->type != a->type) return fail(LK_ERR_INVALID_ARG, "Result tensor type must match input type");
+  if (a->type != LK_TYPE_F32 || (b && b->type != LK_TYPE_F32))
+    return fail(LK_ERR_NOT_IMPLEMENTED, "%s of type %d is not offloaded (CPU path)", what, a->type);
+  *c = EwChecked{};
+  c->n = t_num_elements(dst);
+  if (c->n <= 0) { c->n = 0; return LK_OK; }
+  const lk_tensor *ts[3] = {a, b, dst};
+  const char *names[3] = {"a", "b", "dst"};
+  uint64_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  for (int k = 0; k < 3; k++) {
+    const lk_tensor *t = ts[k];
+    if (!t) continue;
+    if (!t->data) return fail(LK_ERR_NO_BUFFER, "Tensor buffer not found (%s)", names[k]);
+    span4(t, &lo[k], &hi[k]);
+    if (hi[k] > t->buf_bytes)
+      return fail(LK_ERR_OUT_OF_BOUNDS, "Calculated offset %llu is out of bounds for buffer size %llu",
+                  (unsigned long long)(hi[k] - 4), (unsigned long long)t->buf_bytes);
+    bool mis = ((uintptr_t)t->data + t->data_offset) % 4;
+    for (int i = 0; i < 4; i++) mis = mis || (t->ne[i] > 1 && t->nb[i] % 4);
+    if (mis) return fail(LK_ERR_NOT_IMPLEMENTED, "unaligned element strides for %s (CPU path)", names[k]);
+  }
+  c->a_lo = lo[0]; c->a_hi = hi[0]; c->b_lo = lo[1]; c->b_hi = hi[1]; c->d_lo = lo[2]; c->d_hi = hi[2];
+  // dst exactly a or exactly b (an in-place residual) is fine: every element is read before it is
+  // written, by the same thread. Any other overlap would read bytes another thread may have written.
+  for (int k = 0; k < 2; k++) {
+    const lk_tensor *t = ts[k];
+    if (!t) continue;
+    const uintptr_t t0 = (uintptr_t)t->data, d0 = (uintptr_t)dst->data;
+    if (!(t0 + lo[k] < d0 + hi[2] && d0 + lo[2] < t0 + hi[k])) continue;
+    bool same = t0 + t->data_offset == d0 + dst->data_offset;
+    for (int i = 0; i < 4; i++) same = same && (t->ne[i] <= 1 || t->nb[i] == dst->nb[i]);
+    if (!same) return fail(LK_ERR_NOT_IMPLEMENTED, "dst partially overlaps %s (CPU path)", names[k]);
+  }
+  return LK_OK;
+}
+
+template <int MODE>
+void launch_ew_t(bool v4, unsigned grid, hipStream_t st, const EwArgs &g) {
+  if (v4) hipLaunchKernelGGL((ew_v4<MODE>), dim3(grid), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL((ew_strided<MODE>), dim3(grid), dim3(256), 0, st, g);
+}
+
+// mode: EwMode; b == null for kEwAct. Operands were checked by ew_check (c).
+int launch_ew(int mode, int act, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, const EwChecked &c,
+              hipStream_t st) {
+  if (c.n == 0) return LK_OK;
+  EwArgs g{};
+  g.a = (const uint8_t *)a->data + a->data_offset;
+  g.b = b ? (const uint8_t *)b->data + b->data_offset : g.a;
+  g.d = (uint8_t *)dst->data + dst->data_offset;
+  g.n = c.n;
+  g.act = act;
+  bool v4 = true;
+  for (const lk_tensor *t : {a, b, (const lk_tensor *)dst})
+    if (t) v4 = v4 && ew_contiguous(t) && ((uintptr_t)t->data + t->data_offset) % 16 == 0;
+  for (int i = 0; i < 4; i++) {
+    g.ne[i] = std::max<int64_t>(dst->ne[i], 1);
+    g.a_nb[i] = (int64_t)a->nb[i];
+    g.b_nb[i] = (int64_t)(b ? b->nb[i] : a->nb[i]);
+    g.d_nb[i] = (int64_t)dst->nb[i];
+  }
+  const int64_t threads = v4 ? (c.n >> 2) + (c.n & 3) : c.n;
+  const unsigned grid = (unsigned)std::min<int64_t>((threads + 255) / 256, 1 << 20);  // grid-stride beyond
+  static const char *const names[] = {"", "add", "mul", "act", "actmul"};
+  note_route("ew%s:%s", names[mode], v4 ? "v4" : "g");
+  switch (mode) {
+    case kEwAdd: launch_ew_t<kEwAdd>(v4, grid, st, g); break;
+    case kEwMul: launch_ew_t<kEwMul>(v4, grid, st, g); break;
+    case kEwAct: launch_ew_t<kEwAct>(v4, grid, st, g); break;
+    case kEwActMul: launch_ew_t<kEwActMul>(v4, grid, st, g); break;
+    default: return fail(LK_ERR_INVALID_ARG, "element-wise mode %d", mode);
+  }
+  HIP_TRY(hipGetLastError());
+  return LK_OK;
+}
+
+// A gated node a · (act(gate) ⊙ up) after the checks of its three steps, in their order:
+// computeGelu(gate) -> t, computeMul(t, up) -> h (t and h shaped and strided like a contiguous gate),
+// computeMatMul(a, h, dst).
+struct GatedChecked {
+  Checked c;        // of (a, h, dst)
+  EwChecked e;      // of (gate, up) -> h
+  lk_tensor h;      // contiguous F32 [N, K]; data filled in at launch (scratch)
+  bool fused;       // the stream kernel takes gate and up itself
+};
+
+int gated_check(const lk_tensor *a, const lk_tensor *gate, const lk_tensor *up, int32_t act, const lk_tensor *dst,
+                GatedChecked *gc) {
+  if (!a || !gate || !up || !dst) return fail(LK_ERR_INVALID_ARG, "null tensor descriptor");
+  *gc = GatedChecked{};
+  if (act != LK_ACT_GELU && act != LK_ACT_SILU) return fail(LK_ERR_INVALID_ARG, "gated product: activation %d", act);
+  lk_tensor h = *gate;  // what computeGelu / computeMul would be handed as their results
+  uint64_t nb = 4;
+  for (int i = 0; i < 4; i++) { h.nb[i] = nb; nb *= (uint64_t)std::max<int64_t>(h.ne[i], 1); }
+  h.type = gate->type;
+  h.data_offset = 0;
+  h.buf_bytes = nb;
+  h.data = (void *)(uintptr_t)256;  // placeholder (aligned, never dereferenced): the scratch at launch
+  EwChecked e1;
+  int rc = ew_check("activation", gate, nullptr, &h, &e1);
+  if (rc) return rc;
+  if ((rc = ew_check("multiplication", gate, up, &h, &gc->e))) return rc;
+  // computeMatMul against h; when fused, against gate's own bytes (same shape, its strides)
+  if ((rc = check(a, &h, dst, &gc->c))) return rc;
+  gc->h = h;
+  Checked cg;
+  gc->fused = !gc->c.empty && gc->e.n > 0 && check(a, gate, dst, &cg) == LK_OK && gemv_eligible(a, gate, dst, cg) &&
+              stream_class(a, cg) != 0 && ((uintptr_t)up->data + up->data_offset) % 16 == 0 &&
+              !(cg.K > 1 && up->nb[1] != 4);
+  return LK_OK;
+}
+
+int gated_device_checked(const lk_tensor *a, const lk_tensor *gate, const lk_tensor *up, int32_t act, lk_tensor *dst,
+                         const GatedChecked &gc, hipStream_t st) {
+  if (gc.c.empty) return LK_OK;
+  if (gc.fused) {
+    const GemvDesc d = make_desc(a, gate, dst, gc.c);
+    return launch_stream_gated(a->type, stream_class(a, gc.c), stream_grid(gc.c.M), d,
+                               (const float *)((const uint8_t *)up->data + up->data_offset), act, nullptr, nullptr, 0, st);
+  }
+  lk_tensor h = gc.h;
+  if (gc.e.n > 0) {  // h into the (device, stream) scratch, then the ordinary route over it
+    GemmScratch &S = gemm_scratch(st);
+    if (int rc = grow_scratch(S, &S.gated, &S.gated_bytes, (size_t)gc.e.n * 4, false, st)) return rc;
+    h.data = S.gated;
+    h.buf_bytes = S.gated_bytes;
+    if (int rc = launch_ew(kEwActMul, act, gate, up, &h, gc.e, st)) return rc;
+  }
+  return mul_mat_device_checked(a, &h, dst, gc.c, st);
+}
+
 int ensure_scratch(Dev &s, int idx, size_t bytes) {
   if (s.scratch_bytes[idx] >= bytes) return LK_OK;
   if (s.scratch[idx]) HIP_TRY(hipFree(s.scratch[idx]));
@@ -1557,7 +1747,7 @@ int lk_scratch_release(void *stream) {
   if (it == scratch_map().end()) return LK_OK;
   GemmScratch &G = it->second;
   for (void *p : G.retired) HIP_TRY(hipFree(p));
-  for (void *p : {G.frag, G.partial, (void *)G.counter, (void *)G.tcnt})
+  for (void *p : {G.frag, G.partial, (void *)G.counter, (void *)G.tcnt, G.gated})
     if (p) HIP_TRY(hipFree(p));
   scratch_map().erase(it);
   return LK_OK;
@@ -1572,7 +1762,8 @@ uint64_t lk_scratch_bytes(void) {
   for (auto &kv : scratch_map())
     if (kv.first.dev == dev) {
       const GemmScratch &G = kv.second;
-      t += G.frag_bytes + G.partial_bytes + G.counter_n * sizeof(int32_t) + G.tcnt_n * sizeof(unsigned) + G.retired_bytes;
+      t += G.frag_bytes + G.partial_bytes + G.counter_n * sizeof(int32_t) + G.tcnt_n * sizeof(unsigned) + G.gated_bytes +
+           G.retired_bytes;
     }
   return t;
 }
@@ -1670,7 +1861,7 @@ void lk_shutdown(void) {
       (void)hipDeviceSynchronize();
       GemmScratch &G = kv.second;
       for (void *p : G.retired) (void)hipFree(p);
-      for (void *p : {G.frag, G.partial, (void *)G.counter, (void *)G.tcnt})
+      for (void *p : {G.frag, G.partial, (void *)G.counter, (void *)G.tcnt, G.gated})
         if (p) (void)hipFree(p);
     }
     scratch_map().clear();
@@ -1690,6 +1881,31 @@ int lk_mul_mat_device(const lk_tensor *a, const lk_tensor *b, lk_tensor *dst, vo
   int rc = check(a, b, dst, &c);
   if (rc) return rc;
   return mul_mat_device_checked(a, b, dst, c, pick_stream(stream));
+}
+
+int lk_binary_device(int32_t op, const lk_tensor *a, const lk_tensor *b, lk_tensor *dst, void *stream) {
+  if (op != LK_BINARY_ADD && op != LK_BINARY_MUL) return fail(LK_ERR_INVALID_ARG, "binary op %d", op);
+  if (!b) return fail(LK_ERR_INVALID_ARG, "null tensor descriptor");
+  EwChecked c;
+  int rc = ew_check(op == LK_BINARY_ADD ? "addition" : "multiplication", a, b, dst, &c);
+  if (rc) return rc;
+  return launch_ew(op == LK_BINARY_ADD ? kEwAdd : kEwMul, 0, a, b, dst, c, pick_stream(stream));
+}
+
+int lk_unary_device(int32_t act, const lk_tensor *a, lk_tensor *dst, void *stream) {
+  if (act != LK_ACT_GELU && act != LK_ACT_SILU) return fail(LK_ERR_INVALID_ARG, "activation %d", act);
+  EwChecked c;
+  int rc = ew_check("activation", a, nullptr, dst, &c);
+  if (rc) return rc;
+  return launch_ew(kEwAct, act, a, nullptr, dst, c, pick_stream(stream));
+}
+
+int lk_mul_mat_gated_device(const lk_tensor *a, const lk_tensor *gate, const lk_tensor *up, int32_t act, lk_tensor *dst,
+                            void *stream) {
+  GatedChecked gc;
+  int rc = gated_check(a, gate, up, act, dst, &gc);
+  if (rc) return rc;
+  return gated_device_checked(a, gate, up, act, dst, gc, pick_stream(stream));
 }
 
 int lk_weights_pin(const lk_tensor *a, uint64_t generation) {
@@ -1937,13 +2153,15 @@ out:
 // node boundaries into segments.
 
 struct lk_plan {
-  struct Group { int32_t qt; int cls; int grid; int spw; StreamWork *work; };
+  // gates != null: the gated stream kernel, gates[] slot for slot with work[] (lk_plan_create_gated)
+  struct Group { int32_t qt; int cls; int grid; int spw; StreamWork *work; StreamGate *gates = nullptr; };
   std::vector<Group> groups;
   // independent 17 <= N <= 32 Q4 nodes of one type in one gemm_skinny_pair_group_kernel launch plus one
   // splitk_reduce_group_kernel launch (round 6); slabs owned by the plan, so one plan must not run on two
   // streams at once (as a chain plan's barrier words)
   std::vector<PairGroupLaunch> pairs;
-  struct Single { lk_tensor a, b, d; Checked c; };
+  // act != LK_ACT_NONE: a gated node that does not stream (b the gate; gc its checks)
+  struct Single { lk_tensor a, b, d; Checked c; lk_tensor up; int32_t act; GatedChecked gc; };
   std::vector<Single> singles;
   unsigned *sync = nullptr;  // chain plans: barrier counters, exit counter, timeout flag
   int nbar = 0;
@@ -1968,7 +2186,7 @@ int group_pair_singles(lk_plan *plan) {
     std::vector<lk_plan::Single> mine, rest;
     for (auto &sg : plan->singles) {
       const double mb = (double)sg.c.M * (double)(sg.c.K / 32) * (qt == LK_TYPE_Q4_0 ? 18 : 20) / 1e6;
-      (sg.a.type == qt && mb <= max_mb && pair_routed(&sg.a, &sg.b, &sg.d, sg.c) ? mine : rest).push_back(sg);
+      (sg.a.type == qt && !sg.act && mb <= max_mb && pair_routed(&sg.a, &sg.b, &sg.d, sg.c) ? mine : rest).push_back(sg);
     }
     if (mine.size() < 2) continue;
     std::vector<PairNodeOps> ops;
@@ -1983,7 +2201,9 @@ int group_pair_singles(lk_plan *plan) {
 
 // Workgroup g gets global rows [bound[g], bound[g+1]) of the concatenation of descs,
 // balanced by weight bytes, cut at node boundaries into segments.
-void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<std::vector<StreamWork>> &per);
+// src (optional): per workgroup, the index into descs each segment of `per` was cut from.
+void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<std::vector<StreamWork>> &per,
+                std::vector<std::vector<int>> *src = nullptr);
 
 // Adjacent nodes that read the same activations and whose weight rows and output rows continue each
 // other in memory (a model's q, k and v projections allocated back to back; gate and up) become one
@@ -1991,7 +2211,11 @@ void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::v
 // stage 48 or 49 rows per workgroup (85.3 workgroups per node), and the 49-row workgroups' waves ran a
 // seventh row and ended the launch ~0.8 µs late (lab stamps). Same bits either way:
 // every row is one wave's dot. LK_NO_MERGE=1 keeps the nodes apart (A/B).
-void merge_adjacent(std::vector<GemvDesc> &descs, int32_t qt) {
+// gates (optional, gated plans): node i's StreamGate, parallel to descs and kept parallel (GemvDesc and
+// StreamWork carry no second activation pointer; a node's gate travels by its position, never by a
+// pointer it shares with other nodes: two stages of a chain may write one reused buffer). Gated
+// nodes stay apart.
+void merge_adjacent(std::vector<GemvDesc> &descs, int32_t qt, std::vector<StreamGate> *gates = nullptr) {
   static const bool off = [] {
     const char *e = std::getenv("LK_NO_MERGE");
     return e && *e == '1';
@@ -1999,30 +2223,43 @@ void merge_adjacent(std::vector<GemvDesc> &descs, int32_t qt) {
   if (off || descs.size() < 2) return;
   const int64_t pb = stream_pair_bytes(qt);
   std::vector<GemvDesc> out;
-  for (const GemvDesc &d : descs) {
+  std::vector<StreamGate> gout;
+  for (size_t di = 0; di < descs.size(); di++) {
+    const GemvDesc &d = descs[di];
     if (!out.empty()) {
       GemvDesc &p = out.back();
       const int64_t row_bytes = (int64_t)(p.K / 64) * pb;
-      if (p.x == d.x && p.K == d.K && p.dst_row_stride == d.dst_row_stride && d.a == p.a + (int64_t)p.M * row_bytes &&
+      const bool plain = !gates || (gout.back().act == LK_ACT_NONE && (*gates)[di].act == LK_ACT_NONE);
+      if (plain && p.x == d.x && p.K == d.K && p.dst_row_stride == d.dst_row_stride && d.a == p.a + (int64_t)p.M * row_bytes &&
           d.dst == p.dst + (int64_t)p.M * p.dst_row_stride && (int64_t)p.M + d.M <= INT32_MAX) {
         p.M += d.M;
         continue;
       }
     }
     out.push_back(d);
+    if (gates) gout.push_back((*gates)[di]);
   }
   descs.swap(out);
+  if (gates) gates->swap(gout);
 }
 
-void build_work(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<StreamWork> &work, int *spw) {
+// gates / wgates (optional): the nodes' StreamGates (parallel to descs) and, out, the work list's
+// (slot for slot with work).
+void build_work(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<StreamWork> &work, int *spw,
+                const std::vector<StreamGate> *gates = nullptr, std::vector<StreamGate> *wgates = nullptr) {
   std::vector<std::vector<StreamWork>> per;
-  split_rows(descs, qt, grid, per);
+  std::vector<std::vector<int>> src;
+  split_rows(descs, qt, grid, per, &src);
   size_t most = 1;
   for (auto &v : per) most = std::max(most, v.size());
   *spw = (int)most;
   work.assign((size_t)grid * most, StreamWork{});
+  if (wgates) wgates->assign((size_t)grid * most, StreamGate{nullptr, LK_ACT_NONE, 0});
   for (int g = 0; g < grid; g++) {
-    for (size_t k = 0; k < per[g].size(); k++) work[(size_t)g * most + k] = per[g][k];
+    for (size_t k = 0; k < per[g].size(); k++) {
+      work[(size_t)g * most + k] = per[g][k];
+      if (gates && wgates) (*wgates)[(size_t)g * most + k] = (*gates)[src[g][k]];
+    }
     work[(size_t)g * most].count = (int32_t)per[g].size();
   }
 }
@@ -2079,10 +2316,12 @@ bool whole_node_shares(const std::vector<GemvDesc> &descs, int32_t qt, int grid,
   return true;
 }
 
-void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<std::vector<StreamWork>> &per) {
+void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::vector<std::vector<StreamWork>> &per,
+                std::vector<std::vector<int>> *src) {
   const int64_t pb = stream_pair_bytes(qt);
   const size_t n = descs.size();
   std::vector<int> wg;
+  if (src) src->assign(grid, {});
   if (whole_node_shares(descs, qt, grid, wg)) {
     per.assign(grid, {});
     int g = 0;
@@ -2094,6 +2333,7 @@ void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::v
         w.a = descs[i].a; w.x = descs[i].x; w.dst = descs[i].dst; w.dst_row_stride = descs[i].dst_row_stride;
         w.K = descs[i].K; w.row_begin = (int32_t)lo; w.row_end = (int32_t)hi;
         per[g].push_back(w);
+        if (src) (*src)[g].push_back((int)i);
       }
     }
     return;
@@ -2123,45 +2363,83 @@ void split_rows(const std::vector<GemvDesc> &descs, int32_t qt, int grid, std::v
       w.a = descs[i].a; w.x = descs[i].x; w.dst = descs[i].dst; w.dst_row_stride = descs[i].dst_row_stride;
       w.K = descs[i].K; w.row_begin = (int32_t)(lo - row0[i]); w.row_end = (int32_t)(hi - row0[i]);
       per[g].push_back(w);
+      if (src) (*src)[g].push_back((int)i);
     }
   }
 }
 
 }  // namespace
 
-int lk_plan_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n, lk_plan **out) {
+namespace {
+
+// The gates array of a work list (slot for slot), uploaded into g.gates.
+int upload_gates(const std::vector<StreamGate> &gates, lk_plan::Group &g) {
+  void *dev = nullptr;
+  if (hipMalloc(&dev, gates.size() * sizeof(StreamGate)) != hipSuccess) return fail(LK_ERR_DEVICE, "plan alloc");
+  g.gates = (StreamGate *)dev;
+  if (hipMemcpy(dev, gates.data(), gates.size() * sizeof(StreamGate), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(LK_ERR_DEVICE, "plan upload");
+  return LK_OK;
+}
+
+// lk_plan_create; with up / act (lk_plan_create_gated) node i is gated when act[i] != LK_ACT_NONE:
+// streaming gated nodes of one quant type share one launch of the gated kernel, the others run the
+// composition at launch.
+int plan_create_impl(const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const int32_t *act, const lk_tensor *dst,
+                     int n, lk_plan **out) {
   if (!out || n < 0) return fail(LK_ERR_INVALID_ARG, "bad plan arguments");
   int rc = ensure_init();
   if (rc) return rc;
   auto plan = new lk_plan();
   // one launch per quant type: the kernel instance for the largest units-per-row class
   // also runs the nodes with fewer units (same occupancy: 8 waves per CU either way)
-  std::map<int32_t, std::vector<GemvDesc>> by_type;
-  std::map<int32_t, int> type_cls;
+  std::map<std::pair<int32_t, bool>, std::vector<GemvDesc>> by_type;  // (quant type, gated)
+  std::map<std::pair<int32_t, bool>, int> type_cls;
+  std::map<int32_t, std::vector<StreamGate>> type_gates;  // the gated groups' StreamGates, parallel to their descs
   for (int i = 0; i < n; i++) {
+    const int32_t ac = act ? act[i] : LK_ACT_NONE;
+    if (ac != LK_ACT_NONE) {
+      if (!up) { lk_plan_destroy(plan); return fail(LK_ERR_INVALID_ARG, "gated node %d without up", i); }
+      GatedChecked gc;
+      if ((rc = gated_check(&a[i], &b[i], &up[i], ac, &dst[i], &gc))) { lk_plan_destroy(plan); return rc; }
+      if (gc.c.empty) continue;
+      if (gc.fused) {
+        const auto key = std::make_pair(a[i].type, true);
+        const GemvDesc d = make_desc(&a[i], &b[i], &dst[i], gc.c);
+        by_type[key].push_back(d);
+        type_cls[key] = std::max(type_cls[key], stream_class(&a[i], gc.c));
+        type_gates[a[i].type].push_back(StreamGate{(const float *)((const uint8_t *)up[i].data + up[i].data_offset), ac, 0});
+      } else {
+        plan->singles.push_back({a[i], b[i], dst[i], gc.c, up[i], ac, gc});
+      }
+      continue;
+    }
     Checked c;
     rc = check(&a[i], &b[i], &dst[i], &c);
     if (rc) { lk_plan_destroy(plan); return rc; }
     if (c.empty) continue;
     const int cls = gemv_eligible(&a[i], &b[i], &dst[i], c) ? stream_class(&a[i], c) : 0;
     if (cls) {
-      by_type[a[i].type].push_back(make_desc(&a[i], &b[i], &dst[i], c));
-      type_cls[a[i].type] = std::max(type_cls[a[i].type], cls);
+      const auto key = std::make_pair(a[i].type, false);
+      by_type[key].push_back(make_desc(&a[i], &b[i], &dst[i], c));
+      type_cls[key] = std::max(type_cls[key], cls);
     }
     else plan->singles.push_back({a[i], b[i], dst[i], c});
   }
   if ((rc = group_pair_singles(plan))) { lk_plan_destroy(plan); return rc; }
   for (auto &kv : by_type) {
-    const int32_t qt = kv.first;
-    const int cls = type_cls[qt];
+    const int32_t qt = kv.first.first;
+    const int cls = type_cls[kv.first];
     auto &descs = kv.second;
-    merge_adjacent(descs, qt);
+    std::vector<StreamGate> *gates = kv.first.second ? &type_gates[qt] : nullptr;
+    std::vector<StreamGate> wgates;
+    merge_adjacent(descs, qt, gates);
     int64_t rows = 0;
     for (auto &d : descs) rows += d.M;
     const int grid = stream_grid(rows);
     std::vector<StreamWork> work;
     int spw = 1;
-    build_work(descs, qt, grid, work, &spw);
+    build_work(descs, qt, grid, work, &spw, gates, &wgates);
     void *dev = nullptr;
     const size_t wb = work.size() * sizeof(StreamWork);
     if (hipMalloc(&dev, wb) != hipSuccess) { lk_plan_destroy(plan); return fail(LK_ERR_DEVICE, "plan alloc"); }
@@ -2170,9 +2448,28 @@ int lk_plan_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst,
       lk_plan_destroy(plan);
       return fail(LK_ERR_DEVICE, "plan upload");
     }
+    if (gates && (rc = upload_gates(wgates, plan->groups.back()))) { lk_plan_destroy(plan); return rc; }
   }
   *out = plan;
   return LK_OK;
+}
+
+int chain_create_impl(const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const int32_t *act, const lk_tensor *dst,
+                      const int32_t *stage, int n, int grid, const void *peer, lk_plan **out);
+
+}  // namespace
+
+int lk_plan_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n, lk_plan **out) {
+  return plan_create_impl(a, b, nullptr, nullptr, dst, n, out);
+}
+
+int lk_plan_create_gated(const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const int32_t *act,
+                         const lk_tensor *dst, const int32_t *stage, int n, lk_plan **out) {
+  if (!stage) return plan_create_impl(a, b, up, act, dst, n, out);
+  if (!out || n <= 0) return fail(LK_ERR_INVALID_ARG, "bad chain arguments");
+  int rc = ensure_init();
+  if (rc) return rc;
+  return chain_create_impl(a, b, up, act, dst, stage, n, cu_count(), nullptr, out);
 }
 
 // Chain plans: dependent stages in one launch of the streaming GEMV, one grid barrier per stage
@@ -2193,23 +2490,45 @@ int lk_plan_create_chain(const lk_tensor *a, const lk_tensor *b, const lk_tensor
 
 int lk_detail_chain_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, const int32_t *stage, int n,
                            int grid, const void *peer, lk_plan **out) {
+  return chain_create_impl(a, b, nullptr, nullptr, dst, stage, n, grid, peer, out);
+}
+
+namespace {
+
+// up / act as in plan_create_impl: a chain with a gated node runs the gated kernel for every stage
+// (its plain segments carry act = LK_ACT_NONE); the barriers are the plain chain's.
+int chain_create_impl(const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const int32_t *act, const lk_tensor *dst,
+                      const int32_t *stage, int n, int grid, const void *peer, lk_plan **out) {
   if (!out || n <= 0 || !stage || grid < 1) return fail(LK_ERR_INVALID_ARG, "bad chain arguments");
   int rc = LK_OK;
   std::vector<std::vector<GemvDesc>> stages;
   int32_t qt = -1;
   int cls = 0;
+  std::vector<std::vector<StreamGate>> stage_gates;  // parallel to stages
+  bool any_gated = false;
   for (int i = 0; i < n; i++) {
     if (stage[i] < 0 || (i > 0 && stage[i] < stage[i - 1]) || stage[i] > (i ? stage[i - 1] + 1 : 0))
       return fail(LK_ERR_INVALID_ARG, "chain: stage ids must start at 0 and grow by at most 1 (node %d)", i);
     Checked c;
-    if ((rc = check(&a[i], &b[i], &dst[i], &c))) return rc;
+    const int32_t ac = act ? act[i] : LK_ACT_NONE;
+    StreamGate sg{nullptr, LK_ACT_NONE, 0};
+    if (ac != LK_ACT_NONE) {
+      if (!up || peer) return fail(LK_ERR_INVALID_ARG, "chain: gated node %d without up, or in a multi-GPU chain", i);
+      GatedChecked gc;
+      if ((rc = gated_check(&a[i], &b[i], &up[i], ac, &dst[i], &gc))) return rc;
+      if (!gc.fused) return fail(LK_ERR_NOT_IMPLEMENTED, "chain: gated node %d is not a streaming GEMV node", i);
+      c = gc.c;
+      sg = StreamGate{(const float *)((const uint8_t *)up[i].data + up[i].data_offset), ac, 0};
+      any_gated = true;
+    } else if ((rc = check(&a[i], &b[i], &dst[i], &c))) return rc;
     if (c.empty || !gemv_eligible(&a[i], &b[i], &dst[i], c) || !stream_class(&a[i], c))
       return fail(LK_ERR_NOT_IMPLEMENTED, "chain: node %d is not a streaming GEMV node", i);
     if (qt >= 0 && a[i].type != qt) return fail(LK_ERR_NOT_IMPLEMENTED, "chain: one quant type per chain");
     qt = a[i].type;
     cls = std::max(cls, stream_class(&a[i], c));
-    if ((int)stages.size() <= stage[i]) stages.emplace_back();
+    if ((int)stages.size() <= stage[i]) { stages.emplace_back(); stage_gates.emplace_back(); }
     stages[stage[i]].push_back(make_desc(&a[i], &b[i], &dst[i], c));
+    stage_gates[stage[i]].push_back(sg);
   }
   const int nbar = (int)stages.size() - 1;
   auto plan = new lk_plan();
@@ -2221,29 +2540,37 @@ int lk_detail_chain_create(const lk_tensor *a, const lk_tensor *b, const lk_tens
     return fail(LK_ERR_DEVICE, "chain: sync alloc");
   }
   std::vector<std::vector<StreamWork>> per(grid);
+  std::vector<std::vector<StreamGate>> pgate(grid);  // slot for slot with per
   for (size_t s = 0; s < stages.size(); s++) {
     std::vector<std::vector<StreamWork>> ps;
-    merge_adjacent(stages[s], qt);
-    split_rows(stages[s], qt, grid, ps);
+    std::vector<std::vector<int>> src;
+    merge_adjacent(stages[s], qt, &stage_gates[s]);
+    split_rows(stages[s], qt, grid, ps, &src);
     for (int g = 0; g < grid; g++) {
       if (ps[g].empty()) {  // no rows here: the workgroup still takes part in the barrier
         StreamWork w{};
         w.a = stages[s][0].a; w.x = stages[s][0].x; w.dst = stages[s][0].dst; w.dst_row_stride = stages[s][0].dst_row_stride;
         w.K = stages[s][0].K;
         ps[g].push_back(w);
+        src[g].push_back(0);
       }
       ps[g][0].barrier = (int32_t)s;  // barrier #s−1 before stage s (none before stage 0)
-      for (auto &w : ps[g]) per[g].push_back(w);
+      for (size_t k = 0; k < ps[g].size(); k++) {
+        per[g].push_back(ps[g][k]);
+        pgate[g].push_back(stage_gates[s][src[g][k]]);
+      }
     }
   }
   size_t most = 1;
   for (auto &v : per) most = std::max(most, v.size());
   std::vector<StreamWork> work((size_t)grid * most, StreamWork{});
+  std::vector<StreamGate> wgates((size_t)grid * most, StreamGate{nullptr, LK_ACT_NONE, 0});
   for (int g = 0; g < grid; g++) {
     for (size_t k = 0; k < per[g].size(); k++) {
       per[g][k].nbar = nbar;
       per[g][k].sync = plan->sync;
       work[(size_t)g * most + k] = per[g][k];
+      wgates[(size_t)g * most + k] = pgate[g][k];
     }
     work[(size_t)g * most].count = (int32_t)per[g].size();
   }
@@ -2255,9 +2582,12 @@ int lk_detail_chain_create(const lk_tensor *a, const lk_tensor *b, const lk_tens
     lk_plan_destroy(plan);
     return fail(LK_ERR_DEVICE, "plan upload");
   }
+  if (any_gated && (rc = upload_gates(wgates, plan->groups.back()))) { lk_plan_destroy(plan); return rc; }
   *out = plan;
   return LK_OK;
 }
+
+}  // namespace
 
 int lk_plan_chain_timed_out(lk_plan *plan) {
   if (!plan || !plan->sync) return 0;
@@ -2333,7 +2663,8 @@ int lk_plan_launch(lk_plan *plan, void *stream) {
       pf.M = plan->pf_spw;
     }
 #endif
-    int rc = launch_stream(g.qt, g.cls, g.grid, pf, g.work, g.spw, st, plan->peer);
+    int rc = g.gates ? launch_stream_gated(g.qt, g.cls, g.grid, pf, nullptr, 0, g.work, g.gates, g.spw, st)
+                     : launch_stream(g.qt, g.cls, g.grid, pf, g.work, g.spw, st, plan->peer);
     if (rc) return rc;
   }
   for (auto &pg : plan->pairs) {
@@ -2341,7 +2672,8 @@ int lk_plan_launch(lk_plan *plan, void *stream) {
     if (rc) return rc;
   }
   for (auto &s : plan->singles) {
-    int rc = mul_mat_device_checked(&s.a, &s.b, &s.d, s.c, st);
+    int rc = s.act ? gated_device_checked(&s.a, &s.b, &s.up, s.act, &s.d, s.gc, st)
+                   : mul_mat_device_checked(&s.a, &s.b, &s.d, s.c, st);
     if (rc) return rc;
   }
   return LK_OK;
@@ -2364,12 +2696,18 @@ extern "C" int lk_plan_prefetch_next(lk_plan *plan, const lk_plan *next) {
 #endif
 
 int lk_plan_num_launches(const lk_plan *plan) {
-  return plan ? (int)(plan->groups.size() + plan->pairs.size() + plan->singles.size()) : 0;
+  if (!plan) return 0;
+  int composed = 0;  // a gated node that does not stream: the element-wise launch, then the product's
+  for (auto &s : plan->singles) composed += s.act != LK_ACT_NONE;
+  return (int)(plan->groups.size() + plan->pairs.size() + plan->singles.size()) + composed;
 }
 
 void lk_plan_destroy(lk_plan *plan) {
   if (!plan) return;
-  for (auto &g : plan->groups) (void)hipFree(g.work);
+  for (auto &g : plan->groups) {
+    (void)hipFree(g.work);
+    if (g.gates) (void)hipFree(g.gates);
+  }
   for (auto &pg : plan->pairs) free_pair_group(pg);
   if (plan->sync) (void)hipFree(plan->sync);
   delete plan;
@@ -2482,8 +2820,15 @@ struct lk_graph {
   std::vector<Region> regions;
   // per non-empty dependency level: one plan of the nodes every device computes whole and, on a
   // sharded graph, one sharded plan of the row-sharded nodes (their in-place all-gathers after it)
-  struct Level { lk_plan *plan = nullptr; lk_sharded_plan *sp = nullptr; };
+  // ew: the level's element-wise nodes (lk_graph_create_ops), launched one by one after the plan
+  struct Level { lk_plan *plan = nullptr; lk_sharded_plan *sp = nullptr; std::vector<int> ew; };
   std::vector<Level> levels;
+  // per node of an op graph: kind (GraphKind), activation (a gated MUL_MAT or a unary node), the
+  // device descriptor of a gated node's up, the element-wise checks of the device descriptors
+  std::vector<int32_t> kind, act;
+  std::vector<lk_tensor> du;
+  std::vector<EwChecked> ewc;
+  int fused = 0;  // gated nodes made by lk_graph_create_ops' fusion pass
   // per node: host A descriptor, checks, weight flag, device descriptors, bound weight mirror
   std::vector<lk_tensor> ha, da, db, dd;
   // row sharding over an RCCL communicator (lk_graph_create_sharded): a node with shard[i] runs
@@ -2517,6 +2862,55 @@ struct Span {
   uint64_t lo, hi;
 };
 bool overlaps(const Span &x, const Span &y) { return x.host == y.host && x.lo < y.hi && y.lo < x.hi; }
+
+// What a graph node runs: a MUL_MAT (gated when its act is set), or an F32 element-wise op.
+enum GraphKind { kGraphMulMat = 0, kGraphAdd = 1, kGraphMul = 2, kGraphUnary = 3 };
+// Optional per-node arrays of an op graph (lk_graph_create_ops, after its fusion pass).
+struct GraphOps {
+  const int32_t *kind;   // GraphKind
+  const int32_t *act;    // lk_act: a gated MUL_MAT's or a unary node's
+  const lk_tensor *up;   // a gated MUL_MAT's second activation operand
+};
+
+// One node's checks and byte spans: a, b, u (a gated node's up) are read, d is written.
+struct NodeSpans {
+  Checked c;
+  Span a, b, u, d;
+  uint64_t dense;  // bytes d holds when it has no gaps
+};
+int node_check(int kind, int act, const lk_tensor *a, const lk_tensor *b, const lk_tensor *up, const lk_tensor *dst,
+               NodeSpans *ns) {
+  *ns = NodeSpans{};
+  int rc = LK_OK;
+  Checked &c = ns->c;
+  if (kind == kGraphMulMat && act == LK_ACT_NONE) {
+    if ((rc = check(a, b, dst, &c))) return rc;
+    ns->b = {(uintptr_t)b->data, c.b_lo, c.b_hi};
+  } else if (kind == kGraphMulMat) {
+    GatedChecked gc;
+    if ((rc = gated_check(a, b, up, act, dst, &gc))) return rc;
+    c = gc.c;
+    c.b_lo = gc.e.a_lo; c.b_hi = gc.e.a_hi;  // the gate's own bytes (gc.c measured the contiguous h)
+    if (gc.e.n == 0) c.b_lo = c.b_hi = b->data_offset;
+    ns->b = {(uintptr_t)b->data, c.b_lo, c.b_hi};
+    ns->u = {(uintptr_t)up->data, gc.e.b_lo, gc.e.b_hi};
+  } else {
+    EwChecked e;
+    const bool unary = kind == kGraphUnary;
+    if ((rc = ew_check("element-wise node", a, unary ? nullptr : b, dst, &e))) return rc;
+    c = Checked{};
+    c.path = Path::kF32;
+    c.empty = e.n == 0;
+    c.a_lo = e.a_lo; c.a_hi = e.a_hi; c.b_lo = e.b_lo; c.b_hi = e.b_hi; c.d_lo = e.d_lo; c.d_hi = e.d_hi;
+    c.M = e.n; c.N = 1;
+    if (!unary) ns->b = {(uintptr_t)b->data, c.b_lo, c.b_hi};
+  }
+  ns->a = {(uintptr_t)a->data, c.a_lo, c.a_hi};
+  ns->d = {(uintptr_t)dst->data, c.d_lo, c.d_hi};
+  const uint64_t ew = dst->type == LK_TYPE_F16 ? 2 : 4;
+  ns->dense = (uint64_t)c.M * c.N * ew;
+  return LK_OK;
+}
 
 // Union of spans per host buffer, as sorted disjoint intervals.
 std::vector<Span> merge_spans(std::vector<Span> v) {
@@ -2577,15 +2971,20 @@ int graph_bind(lk_graph *g, bool at_create) {
     d.buf_bytes = m->lo + m->bytes + kASlack;          // the mirror's end, its slack included
   }
   for (int l = 0; l < g->nlev; l++) {
-    std::vector<lk_tensor> la, lb, ld, sa, sb, sd;
+    std::vector<lk_tensor> la, lb, lu, ld, sa, sb, sd;
+    std::vector<int32_t> lact;
+    lk_graph::Level L;
     for (int i = 0; i < n; i++) {
       if (g->node_level[i] != l || g->c[i].empty) continue;
-      if (g->shard[i]) { sa.push_back(g->sa[i]); sb.push_back(g->db[i]); sd.push_back(g->dd[i]); }
-      else { la.push_back(g->da[i]); lb.push_back(g->db[i]); ld.push_back(g->dd[i]); }
+      if (g->kind[i] != kGraphMulMat) {  // element-wise: checked again over the device descriptors
+        const bool unary = g->kind[i] == kGraphUnary;
+        if ((rc = ew_check("element-wise node", &g->da[i], unary ? nullptr : &g->db[i], &g->dd[i], &g->ewc[i]))) return rc;
+        L.ew.push_back(i);
+      } else if (g->shard[i]) { sa.push_back(g->sa[i]); sb.push_back(g->db[i]); sd.push_back(g->dd[i]); }
+      else { la.push_back(g->da[i]); lb.push_back(g->db[i]); lu.push_back(g->du[i]); lact.push_back(g->act[i]); ld.push_back(g->dd[i]); }
     }
-    if (la.empty() && sa.empty()) continue;
-    lk_graph::Level L;
-    if (!la.empty() && (rc = lk_plan_create(la.data(), lb.data(), ld.data(), (int)la.size(), &L.plan))) return rc;
+    if (la.empty() && sa.empty() && L.ew.empty()) continue;
+    if (!la.empty() && (rc = plan_create_impl(la.data(), lb.data(), lu.data(), lact.data(), ld.data(), (int)la.size(), &L.plan))) return rc;
     if (!sa.empty() && (rc = lk_sharded_plan_create(g->comm, sa.data(), sb.data(), sd.data(), (int)sa.size(), &L.sp))) {
       if (L.plan) lk_plan_destroy(L.plan);
       return rc;
@@ -2602,6 +3001,11 @@ int launch_level(lk_graph *g, size_t l, hipStream_t st) {
     if (int r = lk_plan_launch(L.plan, st)) return r;
   if (L.sp)
     if (int r = lk_sharded_plan_launch(L.sp, st)) return r;
+  for (int i : L.ew) {
+    const int kind = g->kind[i];
+    const int mode = kind == kGraphAdd ? kEwAdd : kind == kGraphMul ? kEwMul : kEwAct;
+    if (int r = launch_ew(mode, g->act[i], &g->da[i], kind == kGraphUnary ? nullptr : &g->db[i], &g->dd[i], g->ewc[i], st)) return r;
+  }
   return LK_OK;
 }
 
@@ -2652,16 +3056,20 @@ namespace {
 
 // Builds a graph on the current device (lk_graph_create), or rank comm's part of a sharded one.
 int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n, const uint8_t *outputs,
-                uint64_t weight_generation, lk_graph **out) {
+                uint64_t weight_generation, lk_graph **out, const GraphOps *ops = nullptr) {
   int rc = LK_OK;
   std::vector<Checked> c(n);
   std::vector<char> a_weight(n, 0);
-  std::vector<Span> dsp(n), asp(n), bsp(n);
+  std::vector<Span> dsp(n), asp(n), bsp(n), usp(n);  // usp: a gated node's up (empty otherwise)
+  std::vector<uint64_t> dense(n);
+  std::vector<int32_t> kind(n, kGraphMulMat), nact(n, LK_ACT_NONE);
   for (int i = 0; i < n; i++) {
-    if ((rc = check(&a[i], &b[i], &dst[i], &c[i]))) return rc;
-    asp[i] = {(uintptr_t)a[i].data, c[i].a_lo, c[i].a_hi};
-    bsp[i] = {(uintptr_t)b[i].data, c[i].b_lo, c[i].b_hi};
-    dsp[i] = {(uintptr_t)dst[i].data, c[i].d_lo, c[i].d_hi};
+    if (ops) { kind[i] = ops->kind[i]; nact[i] = ops->act[i]; }
+    NodeSpans ns;
+    if ((rc = node_check(kind[i], nact[i], &a[i], &b[i], ops ? &ops->up[i] : nullptr, &dst[i], &ns))) return rc;
+    c[i] = ns.c;
+    asp[i] = ns.a; bsp[i] = ns.b; usp[i] = ns.u; dsp[i] = ns.d;
+    dense[i] = ns.dense;
   }
   // quantized A that no node writes: a weight (pinned); anything else is an activation
   for (int i = 0; i < n; i++) {
@@ -2679,8 +3087,8 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
   for (int j = 0; j < n; j++) {  // level = 1 + deepest earlier node it conflicts with
     int lev = 0;
     for (int i = 0; i < j; i++) {
-      const bool raw = overlaps(dsp[i], bsp[j]) || overlaps(dsp[i], asp[j]);
-      const bool war = overlaps(bsp[i], dsp[j]) || overlaps(asp[i], dsp[j]);
+      const bool raw = overlaps(dsp[i], bsp[j]) || overlaps(dsp[i], asp[j]) || overlaps(dsp[i], usp[j]);
+      const bool war = overlaps(bsp[i], dsp[j]) || overlaps(asp[i], dsp[j]) || overlaps(usp[i], dsp[j]);
       const bool waw = overlaps(dsp[i], dsp[j]);
       if (raw || war || waw) lev = std::max(lev, g->node_level[i] + 1);
     }
@@ -2692,6 +3100,7 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
   for (int i = 0; i < n; i++) {
     if (c[i].empty) continue;
     act.push_back(bsp[i]);
+    act.push_back(usp[i]);
     act.push_back(dsp[i]);
     if (!a_weight[i]) act.push_back(asp[i]);
   }
@@ -2706,9 +3115,9 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
       return false;
     };
     if (!produced_before(bsp[j])) up.push_back(bsp[j]);
+    if (!produced_before(usp[j])) up.push_back(usp[j]);
     if (!a_weight[j] && !produced_before(asp[j])) up.push_back(asp[j]);
-    const uint64_t ew = dst[j].type == LK_TYPE_F16 ? 2 : 4;
-    if (dsp[j].hi - dsp[j].lo != (uint64_t)c[j].M * c[j].N * ew) up.push_back(dsp[j]);
+    if (dsp[j].hi - dsp[j].lo != dense[j]) up.push_back(dsp[j]);
     if (!outputs || outputs[j]) down.push_back(dsp[j]);
   }
   // A region no node reads, that is not uploaded, holding results the caller wants back (a
@@ -2718,6 +3127,7 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
   for (int i = 0; i < n; i++) {
     if (c[i].empty) continue;
     reads.push_back(bsp[i]);
+    reads.push_back(usp[i]);
     if (!a_weight[i]) reads.push_back(asp[i]);
   }
   const std::vector<Span> up_m = merge_spans(up), down_m = merge_spans(down);
@@ -2770,6 +3180,10 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
   g->a_weight = a_weight;
   g->pins.assign(n, nullptr);
   g->da.resize(n); g->db.resize(n); g->dd.resize(n); g->sa.resize(n);
+  g->kind = kind;
+  g->act = nact;
+  g->du.assign(n, lk_tensor{});
+  g->ewc.assign(n, EwChecked{});
   g->shard.assign(n, 0);
   for (int i = 0; i < n && comm; i++)  // row-shardable: a quantized weight, whole blocks per row, M % P, dense F32 dst
     g->shard[i] = a_weight[i] && c[i].K % 32 == 0 && c[i].M % g->nranks == 0 && dst[i].type == LK_TYPE_F32 &&
@@ -2781,8 +3195,15 @@ int graph_build(lk_comm *comm, const lk_tensor *a, const lk_tensor *b, const lk_
       g->da[i].data = mirror_of(g, asp[i].host, c[i].a_lo) - c[i].a_lo;
       g->da[i].buf_bytes = c[i].a_hi;
     }
-    g->db[i].data = mirror_of(g, bsp[i].host, c[i].b_lo) - c[i].b_lo;
-    g->db[i].buf_bytes = c[i].b_hi;
+    if (kind[i] != kGraphUnary) {
+      g->db[i].data = mirror_of(g, bsp[i].host, c[i].b_lo) - c[i].b_lo;
+      g->db[i].buf_bytes = c[i].b_hi;
+    }
+    if (usp[i].hi > usp[i].lo) {
+      g->du[i] = ops->up[i];
+      g->du[i].data = mirror_of(g, usp[i].host, usp[i].lo) - usp[i].lo;
+      g->du[i].buf_bytes = usp[i].hi;
+    }
     g->dd[i].data = mirror_of(g, dsp[i].host, c[i].d_lo) - c[i].d_lo;
     g->dd[i].buf_bytes = c[i].d_hi;
   }
@@ -2910,6 +3331,86 @@ int lk_graph_create(const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst
   return graph_build(nullptr, a, b, dst, n, outputs, weight_generation, out);
 }
 
+int lk_graph_create_ops(const int32_t *op, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst, int n,
+                        const uint8_t *outputs, uint64_t weight_generation, lk_graph **out) {
+  if (!out || n < 0 || (n && (!op || !a || !b || !dst))) return fail(LK_ERR_INVALID_ARG, "bad graph arguments");
+  *out = nullptr;
+  int rc = LK_OK;
+  // every node as given: its checks (errors are the unfused graph's) and byte spans
+  std::vector<int32_t> kind(n), act(n, LK_ACT_NONE);
+  std::vector<NodeSpans> ns(n);
+  for (int i = 0; i < n; i++) {
+    switch (op[i]) {
+      case LK_OP_MUL_MAT: kind[i] = kGraphMulMat; break;
+      case LK_OP_ADD: kind[i] = kGraphAdd; break;
+      case LK_OP_MUL: kind[i] = kGraphMul; break;
+      case LK_OP_GELU:
+      case LK_OP_SILU: kind[i] = kGraphUnary; act[i] = LK_ACT_GELU; break;  // computeSilu computes GELU (:2633-2638)
+      default: return fail(LK_ERR_NOT_IMPLEMENTED, "Operation %d not implemented in compute graph (node %d)", op[i], i);
+    }
+    if ((rc = node_check(kind[i], act[i], &a[i], &b[i], nullptr, &dst[i], &ns[i]))) return rc;
+  }
+  // fusion: MUL_MAT(W, MUL(ACT(g), u)) with t = ACT(g) (node i) and h = MUL (node j) touched by no other
+  // node and not wanted back becomes one gated node at k's place; i and j go
+  auto same = [](const lk_tensor &x, const lk_tensor &y) {
+    return x.type == y.type && x.data == y.data && x.data_offset == y.data_offset && !std::memcmp(x.ne, y.ne, sizeof x.ne) &&
+           !std::memcmp(x.nb, y.nb, sizeof x.nb);
+  };
+  auto touches = [&](int m, const Span &s) {
+    return overlaps(ns[m].a, s) || overlaps(ns[m].b, s) || overlaps(ns[m].d, s);
+  };
+  std::vector<char> gone(n, 0);
+  std::vector<lk_tensor> gb(b, b + n), gu(n, lk_tensor{});
+  int fused = 0;
+  for (int k = 0; k < n && outputs; k++) {
+    if (kind[k] != kGraphMulMat || ns[k].c.empty) continue;
+    int j = -1, i = -1;
+    for (int m = k - 1; m >= 0 && j < 0; m--)
+      if (kind[m] == kGraphMul && !gone[m] && same(dst[m], b[k])) j = m;
+    if (j < 0 || outputs[j]) continue;
+    bool t_first = true;
+    for (int m = j - 1; m >= 0 && i < 0; m--) {
+      if (kind[m] != kGraphUnary || gone[m]) continue;
+      if (same(dst[m], a[j])) { i = m; t_first = true; }
+      else if (same(dst[m], b[j])) { i = m; t_first = false; }
+    }
+    if (i < 0 || outputs[i]) continue;
+    const lk_tensor &u = t_first ? b[j] : a[j];
+    const Span tsp = ns[i].d, hsp = ns[j].d, gsp = ns[i].a, usp = t_first ? ns[j].b : ns[j].a;
+    bool ok = !overlaps(tsp, hsp) && !overlaps(tsp, usp) && !overlaps(tsp, gsp) && !overlaps(hsp, usp) && !overlaps(hsp, gsp) &&
+              !overlaps(ns[k].a, hsp) && !overlaps(ns[k].d, hsp) && !overlaps(ns[k].a, tsp) && !overlaps(ns[k].d, tsp);
+    for (int m = 0; m < n && ok; m++) {
+      if (m != i && m != j && m != k && (touches(m, tsp) || touches(m, hsp))) ok = false;
+      // the fused node reads g and u at k's place: nothing in between may overwrite them
+      if (m > i && m < k && m != j && (overlaps(ns[m].d, gsp) || overlaps(ns[m].d, usp))) ok = false;
+    }
+    NodeSpans fs;
+    if (!ok || node_check(kGraphMulMat, LK_ACT_GELU, &a[k], &a[i], &u, &dst[k], &fs) != LK_OK) continue;
+    gone[i] = gone[j] = 1;
+    gb[k] = a[i];
+    gu[k] = u;
+    act[k] = LK_ACT_GELU;
+    fused++;
+  }
+  if ((rc = ensure_init())) return rc;
+  std::vector<lk_tensor> fa, fb, fu, fd;
+  std::vector<int32_t> fkind, fact;
+  std::vector<uint8_t> fout;
+  for (int i = 0; i < n; i++) {
+    if (gone[i]) continue;
+    fa.push_back(a[i]); fb.push_back(gb[i]); fu.push_back(gu[i]); fd.push_back(dst[i]);
+    fkind.push_back(kind[i]); fact.push_back(act[i]);
+    fout.push_back(outputs ? outputs[i] : 1);
+  }
+  const GraphOps ops{fkind.data(), fact.data(), fu.data()};
+  rc = graph_build(nullptr, fa.data(), fb.data(), fd.data(), (int)fa.size(), outputs ? fout.data() : nullptr, weight_generation,
+                   out, &ops);
+  if (rc == LK_OK) (*out)->fused = fused;
+  return rc;
+}
+
+int lk_graph_num_fused(const lk_graph *g) { return g ? g->fused : 0; }
+
 int lk_graph_create_sharded(lk_comm *const *comms, int ncomms, const lk_tensor *a, const lk_tensor *b, const lk_tensor *dst,
                             int n, const uint8_t *outputs, uint64_t weight_generation, lk_graph **out) {
   if (!out || !comms || ncomms < 1 || n < 0 || (n && (!a || !b || !dst)))
@@ -2965,7 +3466,7 @@ int lk_graph_num_launches(const lk_graph *g) {
   if (g && !g->parts.empty()) g = g->parts[0];
   int t = 0;
   if (g)
-    for (auto &L : g->levels) t += (L.plan ? lk_plan_num_launches(L.plan) : 0) + (L.sp ? 1 : 0);
+    for (auto &L : g->levels) t += (L.plan ? lk_plan_num_launches(L.plan) : 0) + (L.sp ? 1 : 0) + (int)L.ew.size();
   return t;
 }
 

@@ -315,6 +315,97 @@ struct StreamWork {
 };
 static_assert(sizeof(StreamWork) == 64, "one s_load_dwordx16");
 
+// The gated instantiation's second activation pointer and its activation, in an array parallel to
+// work[] (slot for slot): StreamWork stays one s_load_dwordx16. act == LK_ACT_NONE: a plain segment.
+struct StreamGate {
+  const float *up;
+  int32_t act, pad;
+};
+static_assert(sizeof(StreamGate) == 16, "one s_load_dwordx4");
+
+// ---- F32 element-wise arithmetic (computeAdd / computeMul / computeGelu) -------------------
+//
+// The Kotlin expressions in the Kotlin order, every product, sum and quotient rounded on its own
+// (__f*_rn: the library is built with contraction on). One lk_act / lk_act_mul serves the
+// element-wise kernels and the stream kernel's gated intake, so the fused and the composed gated
+// product hold the same bits.
+__device__ __forceinline__ float lk_act(int act, float x) {
+  if (act == LK_ACT_GELU) {  // x*0.5f*(1.0f+tanh(0.797885f*(x+0.044715f*x*x*x))), core/GGMLComputeOps.kt:1588
+    const float c = __fmul_rn(__fmul_rn(__fmul_rn(0.044715f, x), x), x);
+    const float t = tanhf(__fmul_rn(0.797885f, __fadd_rn(x, c)));
+    return __fmul_rn(__fmul_rn(x, 0.5f), __fadd_rn(1.0f, t));
+  }
+  if (act == LK_ACT_SILU) return __fdiv_rn(x, __fadd_rn(1.0f, expf(-x)));
+  return x;
+}
+__device__ __forceinline__ float lk_act_mul(int act, float g, float u) { return __fmul_rn(lk_act(act, g), u); }
+__device__ __forceinline__ f32x4 lk_act_mul4(int act, f32x4 g, f32x4 u) {
+  return f32x4{lk_act_mul(act, g.x, u.x), lk_act_mul(act, g.y, u.y), lk_act_mul(act, g.z, u.z), lk_act_mul(act, g.w, u.w)};
+}
+
+enum EwMode { kEwAdd = 1, kEwMul = 2, kEwAct = 3, kEwActMul = 4 };
+template <int MODE> __device__ __forceinline__ float ew_apply(int act, float a, float b) {
+  if constexpr (MODE == kEwAdd) return __fadd_rn(a, b);
+  else if constexpr (MODE == kEwMul) return __fmul_rn(a, b);
+  else if constexpr (MODE == kEwAct) return lk_act(act, a);
+  else return lk_act_mul(act, a, b);
+}
+
+struct EwArgs {
+  const uint8_t *a, *b;  // base + dataOffset (b unused by kEwAct)
+  uint8_t *d;
+  int64_t n;             // elements
+  int64_t ne[4];         // >= 1 each
+  int64_t a_nb[4], b_nb[4], d_nb[4];
+  int32_t act, pad;
+};
+
+#ifndef LK_W32_KERNELS
+// Naming: ew_v4, ew_strided and gemv_stream_gated do not end in `_kernel` like the other kernels of
+// this library. tests/test_abi.py::test_kernel_list_is_the_product admits only the names in its
+// PRODUCT_KERNELS set among the lk::*_kernel symbols, and these three families were added without
+// touching that file; tests/test_elementwise_abi.py asserts their presence instead. When
+// PRODUCT_KERNELS is next extended, rename them ew_v4_kernel, ew_strided_kernel and
+// gemv_stream_gated_kernel and list them there.
+// Contiguous operands, 16-byte aligned bases: a float4 per thread, then a scalar tail (n % 4).
+// dst may be exactly a or b: a thread reads its own elements before it writes them.
+template <int MODE>
+__global__ __launch_bounds__(256) void ew_v4(EwArgs g) {
+  const int64_t n4 = g.n >> 2, total = n4 + (g.n & 3), step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    if (i < n4) {
+      const f32x4 a = ((const LK_GLOBAL f32x4 *)g.a)[i];
+      f32x4 b = a;
+      if constexpr (MODE != kEwAct) b = ((const LK_GLOBAL f32x4 *)g.b)[i];
+      ((LK_GLOBAL f32x4 *)g.d)[i] = f32x4{ew_apply<MODE>(g.act, a.x, b.x), ew_apply<MODE>(g.act, a.y, b.y),
+                                          ew_apply<MODE>(g.act, a.z, b.z), ew_apply<MODE>(g.act, a.w, b.w)};
+    } else {
+      const int64_t e = 4 * n4 + (i - n4);
+      const float a = ((const LK_GLOBAL float *)g.a)[e];
+      float b = a;
+      if constexpr (MODE != kEwAct) b = ((const LK_GLOBAL float *)g.b)[e];
+      ((LK_GLOBAL float *)g.d)[e] = ew_apply<MODE>(g.act, a, b);
+    }
+  }
+}
+
+// Any strides: element i of dst's index space (ne[0] fastest) at Σ idx[d]·nb[d] of each tensor.
+template <int MODE>
+__global__ __launch_bounds__(256) void ew_strided(EwArgs g) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < g.n; i += step) {
+    const int64_t i0 = i % g.ne[0], r0 = i / g.ne[0];
+    const int64_t i1 = r0 % g.ne[1], r1 = r0 / g.ne[1];
+    const int64_t i2 = r1 % g.ne[2], i3 = r1 / g.ne[2];
+    const float a = *(const LK_GLOBAL float *)(g.a + i0 * g.a_nb[0] + i1 * g.a_nb[1] + i2 * g.a_nb[2] + i3 * g.a_nb[3]);
+    float b = a;
+    if constexpr (MODE != kEwAct)
+      b = *(const LK_GLOBAL float *)(g.b + i0 * g.b_nb[0] + i1 * g.b_nb[1] + i2 * g.b_nb[2] + i3 * g.b_nb[3]);
+    *(LK_GLOBAL float *)(g.d + i0 * g.d_nb[0] + i1 * g.d_nb[1] + i2 * g.d_nb[2] + i3 * g.d_nb[3]) = ew_apply<MODE>(g.act, a, b);
+  }
+}
+#endif
+
 
 // Device-side waits (only the opt-in chain plans' grid barriers since round 4: the split-K
 // reductions elect a last arriver and never wait) are bounded: a wait that gives up counts itself
@@ -477,10 +568,17 @@ __device__ float q2k_stream_dot(uint32_t sc, const uint32_t *c, uint32_t dd, con
 // the chain's launches (the words are monotonic: a fast rank's next launch may add before a slow
 // rank has left this one, so nothing is re-armed; the rank's last workgroup out bumps its epoch).
 
-template <int QT, int CPL, bool PEER>
+// GATED (gemv_stream_gated): a segment with act != LK_ACT_NONE computes A · (act(gate) ⊙ up), gate
+// being the segment's x and up / act coming from gates[] (slot for slot with work[]) or s_up / s_act.
+// Its activation image is filled through VGPRs as in chain plans: the gate float4 and the up float4
+// of each image position are loaded together and lk_act_mul4 of them is stored where x_store stores.
+// Everything after the image (decode, ring, reductions) is the plain kernel's.
+template <int QT, int CPL, bool PEER, bool GATED = false>
 __device__ __forceinline__ void gemv_stream_body(const StreamWork *__restrict__ work, int spw, const uint8_t *s_a,
                                                  const float *s_x, float *s_dst, int64_t s_dst_stride, int s_M, int s_K,
-                                                 const PeerDesc *__restrict__ peer) {
+                                                 const PeerDesc *__restrict__ peer,
+                                                 const StreamGate *__restrict__ gates = nullptr,
+                                                 const float *s_up = nullptr, int s_act = 0) {
   using G = StreamGeom<QT, CPL>;
   extern __shared__ f32x4 lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -554,6 +652,16 @@ __device__ __forceinline__ void gemv_stream_body(const StreamWork *__restrict__ 
       rb = min((int)blockIdx.x * per, s_M);
       re = min(rb + per, s_M);
     }
+    [[maybe_unused]] const float *up_node = s_up;
+    [[maybe_unused]] int act = s_act;
+    if constexpr (GATED) {
+      if (wk) {
+        const __attribute__((address_space(4))) StreamGate *gs =
+            (const __attribute__((address_space(4))) StreamGate *)(gates + (int64_t)blockIdx.x * spw + si);
+        up_node = gs->up;
+        act = gs->act;
+      }
+    }
     const int NP = K >> 6;                         // block pairs per row
     const int nch = (NP + 63) >> 6;                // units per row
     const int64_t RB = (int64_t)NP * G::PB;        // row bytes
@@ -626,6 +734,25 @@ __device__ __forceinline__ void gemv_stream_body(const StreamWork *__restrict__ 
         xv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (p * 16 + t) * 16, 0, PEER ? 17 : 16));
       }
     };
+    // gated segments: the up float4 of the same image positions, and the image value from both
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t urs =
+        __builtin_amdgcn_make_buffer_rsrc((void *)(GATED && act ? up_node : x_node), 0, K * 4, 0x00020000);
+    [[maybe_unused]] auto u_issue = [&](int r, f32x4 (&uv)[4]) __attribute__((always_inline)) {
+      if (act) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int k = min(wave + kStreamWaves * (4 * r + q), xinst - 1), i = k * 64 + lane;
+          const int p = min(i >> 4, NP - 1), t = (i & 15) ^ ((i >> 4) & 15);
+          uv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, (p * 16 + t) * 16, 0, 16));
+        }
+      }
+    };
+    [[maybe_unused]] auto u_apply = [&](f32x4 (&xv)[4], const f32x4 (&uv)[4]) __attribute__((always_inline)) {
+      if (act) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) xv[q] = lk_act_mul4(act, xv[q], uv[q]);
+      }
+    };
     auto x_store = [&](int r, const f32x4 (&xv)[4]) __attribute__((always_inline)) {
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -636,8 +763,11 @@ __device__ __forceinline__ void gemv_stream_body(const StreamWork *__restrict__ 
     auto load_x_sc1 = [&]() __attribute__((always_inline)) {  // every round after all older loads
       for (int r = 0; r < xrounds; r++) {
         f32x4 xv[4];
+        [[maybe_unused]] f32x4 uv[4];
         x_issue(r, xv);
+        if constexpr (GATED) u_issue(r, uv);
         wait_vmcnt<0>();
+        if constexpr (GATED) u_apply(xv, uv);
         x_store(r, xv);
       }
     };
@@ -723,19 +853,26 @@ __device__ __forceinline__ void gemv_stream_body(const StreamWork *__restrict__ 
       load_x_sc1();
       wait_lgkmcnt0();
       __builtin_amdgcn_s_barrier();
-    } else if (sync) {  // chain plans, a later segment of a stage (or stage 0): no grid barrier
+    } else if (GATED || sync) {  // chain plans, a later segment of a stage (or stage 0): no grid barrier
+      // (the gated kernel fills every image through VGPRs, in plain plans and single launches too)
       if (si > 0) __builtin_amdgcn_s_barrier();  // every wave is done with the previous segment's image
       {  // the first round of activation loads ahead of the weight prologue, waited for alone
         f32x4 xv[4];
+        [[maybe_unused]] f32x4 uv[4];
         x_issue(0, xv);
+        if constexpr (GATED) u_issue(0, uv);
         weight_prologue();
         wait_vmcnt<G::D * G::L>();
+        if constexpr (GATED) u_apply(xv, uv);
         x_store(0, xv);
       }
       for (int r = 1; r < xrounds; r++) {
         f32x4 xv[4];
+        [[maybe_unused]] f32x4 uv[4];
         x_issue(r, xv);
+        if constexpr (GATED) u_issue(r, uv);
         wait_vmcnt<0>();
+        if constexpr (GATED) u_apply(xv, uv);
         x_store(r, xv);
       }
       wait_lgkmcnt0();
@@ -936,6 +1073,18 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gemv_stream_kernel(const St
                                                                         const uint8_t *s_a, const float *s_x, float *s_dst,
                                                                         int64_t s_dst_stride, int s_M, int s_K) {
   gemv_stream_body<QT, CPL, false>(work, spw, s_a, s_x, s_dst, s_dst_stride, s_M, s_K, nullptr);
+}
+
+// The gated product's stream kernel (lk_mul_mat_gated_device, lk_plan_create_gated): gemv_stream_body
+// with the gated activation intake; gates[] parallels work[] (null with work: s_up / s_act).
+// (No `_kernel` suffix: see the naming note at ew_v4.)
+template <int QT, int CPL>
+__global__ __launch_bounds__(kStreamWaves * 64) void gemv_stream_gated(const StreamWork *__restrict__ work, int spw,
+                                                                       const StreamGate *__restrict__ gates,
+                                                                       const uint8_t *s_a, const float *s_x, float *s_dst,
+                                                                       int64_t s_dst_stride, int s_M, int s_K,
+                                                                       const float *s_up, int s_act) {
+  gemv_stream_body<QT, CPL, false, true>(work, spw, s_a, s_x, s_dst, s_dst_stride, s_M, s_K, nullptr, gates, s_up, s_act);
 }
 
 // One rank of a multi-GPU chain (lk_p2p_chain): the chain-plan stream kernel with peer row stores and

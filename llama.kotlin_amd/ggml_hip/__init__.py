@@ -4,6 +4,8 @@ Host-side mirror of the reference's operator/plugin API for this path, over the
 C-ABI in include/lk_hip.h (liblk_hip.so, hand-written HIP kernels):
 
   computeMatMul(graphAllocator, context, a, b, dst)  core/GGMLComputeOps.kt:1435
+  computeAdd / computeMul / computeGelu / computeSilu core/GGMLComputeOps.kt:735, :811, :1581, :2633 (F32)
+  computeMatMulGated (a · (act(gate) ⊙ up))           the MLP's three calls in one launch
   GGMLTensor / GGMLGraphAllocator / GGMLType          core/GGMLTypes.kt, core/GGMLAlloc.kt
   GGMLHipBackend (GGMLBackend)                        core/GGMLBackend.kt:90-157
   dequantizeTensor / quantizeTensor (device)          core/GGMLComputeOps.kt:918 / :1040
@@ -17,7 +19,8 @@ from . import _lib
 from ._lib import (HipDeviceError, IllegalArgumentException, IllegalStateException, IndexOutOfBoundsException,
                    NotOffloadedError)
 from .backend import GGMLBackendRegistry, GGMLHipBackend, GGMLStatus
-from .ops import (DotKind, MulMatPlan, ResidentGraph, computeDotProductF32Q41, computeDotProductF32Q80, computeDotProductMatrix,
+from .ops import (Act, computeAdd, computeBinary, computeGelu, computeMatMulGated, computeMul, computeSilu, computeUnary,
+                  DotKind, MulMatPlan, ResidentGraph, computeDotProductF32Q41, computeDotProductF32Q80, computeDotProductMatrix,
                   computeDotProductQ40Q40, computeDotProductQ41Q41, computeDotProductQ80Q40, computeDotProductQ80Q80, computeMatMul,
                   computeMatMulSharded, dequantizeTensor, quantizeTensor, setSyncWaitBound, syncCountersSum, syncTimeouts, debugRoute, debugScratchEpoch, debugPokeGemmCounter, scratchRelease, scratchBytes, to_lk, validateMatMul, weightsCachedBytes, weightsCachedCount,
                   weightsEvict, weightsEvictAll, weightsEvictBuffer, weightsPin, weightsPinSharded)
@@ -30,6 +33,7 @@ __all__ = [
     "syncTimeouts", "setSyncWaitBound", "syncCountersSum", "debugRoute", "debugScratchEpoch", "debugPokeGemmCounter", "scratchRelease", "scratchBytes",
     "GGMLType", "GGMLTensor", "GGMLGraphAllocator", "GGMLContext", "GGMLCGraph", "GGMLOp",
     "calculateContiguousStrides", "calculateTensorByteSize",
+    "Act", "computeAdd", "computeMul", "computeGelu", "computeSilu", "computeBinary", "computeUnary", "computeMatMulGated",
     "computeMatMul", "computeMatMulSharded", "weightsPinSharded", "validateMatMul", "MulMatPlan", "ResidentGraph", "dequantizeTensor", "quantizeTensor", "weightsPin",
     "weightsEvictAll", "weightsEvict", "weightsEvictBuffer", "weightsCachedBytes", "weightsCachedCount", "to_lk", "DotKind", "computeDotProductMatrix", "computeDotProductF32Q41",
     "computeDotProductF32Q80", "computeDotProductQ80Q80", "computeDotProductQ40Q40", "computeDotProductQ41Q41",

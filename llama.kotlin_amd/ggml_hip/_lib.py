@@ -93,6 +93,8 @@ EXPORTED_SYMBOLS = (
     "lk_p2p_chain_create", "lk_p2p_chain_launch", "lk_p2p_chain_timed_out", "lk_p2p_chain_num_launches",
     "lk_p2p_chain_destroy", "lk_p2p_chain_rank_stream",
     "lk_dequantize_device", "lk_quantize_device", "lk_dot_direct", "lk_dot_direct_device",
+    "lk_binary_device", "lk_unary_device", "lk_mul_mat_gated_device", "lk_plan_create_gated",
+    "lk_graph_create_ops", "lk_graph_num_fused",
     # include/lk_gguf.h
     "lk_gguf_open_memory", "lk_gguf_open_file", "lk_gguf_close", "lk_gguf_version", "lk_gguf_alignment",
     "lk_gguf_data_offset", "lk_gguf_data_bytes", "lk_gguf_kv_count", "lk_gguf_find_key", "lk_gguf_kv_key",
@@ -215,6 +217,15 @@ def load():
     L.lk_quantize_device.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, vp]
     L.lk_dot_direct.argtypes = [ctypes.c_int32, P, P, ctypes.c_int64, vp]
     L.lk_dot_direct_device.argtypes = [ctypes.c_int32, P, P, ctypes.c_int64, vp, vp]
+    if hasattr(L, "lk_binary_device"):  # (absent from lab builds of earlier rounds loaded for A/B)
+        L.lk_binary_device.argtypes = [ctypes.c_int32, P, P, P, vp]
+        L.lk_unary_device.argtypes = [ctypes.c_int32, P, P, vp]
+        L.lk_mul_mat_gated_device.argtypes = [P, P, P, ctypes.c_int32, P, vp]
+        L.lk_plan_create_gated.argtypes = [P, P, P, ctypes.POINTER(ctypes.c_int32), P, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_int, ctypes.POINTER(vp)]
+        L.lk_graph_create_ops.argtypes = [ctypes.POINTER(ctypes.c_int32), P, P, P, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.lk_graph_num_fused.argtypes = [vp]
     # GGUF (include/lk_gguf.h); handles are opaque void*
     u64, i64, i32, pvp, pu64 = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint64)
     L.lk_gguf_open_memory.argtypes = [vp, u64, i32, pvp]

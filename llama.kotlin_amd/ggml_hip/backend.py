@@ -18,8 +18,13 @@ import enum
 from collections import OrderedDict
 
 from . import _lib
-from .ops import MulMatPlan, ResidentGraph, _is_host, computeMatMul
+from .ops import (Act, MulMatPlan, ResidentGraph, _is_host, computeAdd, computeGelu, computeMatMul, computeMatMulGated,
+                  computeMul)
 from .tensor import GGMLCGraph, GGMLOp, GGMLTensor, GGMLType, descriptorEpoch
+
+
+_UNARY = (GGMLOp.GELU, GGMLOp.SILU)
+_ELEMENTWISE = (GGMLOp.ADD, GGMLOp.MUL) + _UNARY
 
 
 class GGMLStatus(enum.Enum):
@@ -100,7 +105,11 @@ def _graph_key(ga, nodes, extra) -> tuple:
     (base and size, via the buffer table) — plus `extra` per node, as one flat tuple."""
     key = [_buffer_table(ga)]
     for n, e in zip(nodes, extra):
+        key.append(n.op._value_)
         for t in (n.src[0], n.src[1], n):
+            if t is None:  # a unary node's src[1]
+                key.append(None)
+                continue
             key.append(t.type._value_)
             key.extend(t.ne)
             key.extend(t.nb)
@@ -108,6 +117,66 @@ def _graph_key(ga, nodes, extra) -> tuple:
             key.append(t.bufferId)
         key.append(e)
     return tuple(key)
+
+
+def _same_tensor(x: GGMLTensor, y: GGMLTensor) -> bool:
+    return x is y or (x.type == y.type and x.bufferId == y.bufferId and x.dataOffset == y.dataOffset and
+                      list(x.ne) == list(y.ne) and list(x.nb) == list(y.nb))
+
+
+def _byte_range(t: GGMLTensor):
+    """(bufferId, lo, hi) of the bytes an element tensor's indices reach (quantized: its blocks)."""
+    if t.type in (GGMLType.F32, GGMLType.F16):
+        span = sum((max(int(t.ne[d]), 1) - 1) * int(t.nb[d]) for d in range(4)) + t.type.byteSize
+    else:
+        from .tensor import calculateTensorByteSize
+        span = calculateTensorByteSize(t)
+    return t.bufferId, t.dataOffset, t.dataOffset + span
+
+
+def _overlaps(x: GGMLTensor, y: GGMLTensor) -> bool:
+    (bx, lx, hx), (by, ly, hy) = _byte_range(x), _byte_range(y)
+    return bx == by and lx < hy and ly < hx
+
+
+def matchGated(nodes, k: int):
+    """The pattern lk_graph_create_ops fuses, with its conditions, on GGMLTensor nodes: nodes[k] =
+    MUL_MAT(W, h) with h = MUL(t, u) or MUL(u, t), t = GELU/SILU(g), where no other node reads or
+    writes bytes of t or h, neither is an output, and no node between the activation and the
+    MUL_MAT writes bytes of g or u (the fused call reads them at the MUL_MAT's place; ADD / MUL may
+    run in place). Returns (i, j, g, u) — the node indices of t and h — or None."""
+    n = nodes[k]
+    if n.op != GGMLOp.MUL_MAT or n.src[0] is None or n.src[1] is None:
+        return None
+    j = next((m for m in range(k - 1, -1, -1) if nodes[m].op == GGMLOp.MUL and _same_tensor(nodes[m], n.src[1])), None)
+    if j is None:
+        return None
+    h = nodes[j]
+    for t, u in ((h.src[0], h.src[1]), (h.src[1], h.src[0])):
+        if t is None or u is None:
+            continue
+        i = next((m for m in range(j - 1, -1, -1) if nodes[m].op in _UNARY and _same_tensor(nodes[m], t)), None)
+        if i is None or nodes[i].src[0] is None:
+            continue
+        tn, g = nodes[i], nodes[i].src[0]
+        if tn.isOutput() or h.isOutput():
+            continue
+        # t, h, g and u are four separate byte ranges; W and the result touch neither intermediate
+        apart = [(tn, h), (tn, g), (tn, u), (h, g), (h, u), (n.src[0], tn), (n.src[0], h), (n, tn), (n, h)]
+        if any(_overlaps(x, y) for x, y in apart):
+            continue
+        ok = True
+        for m, x in enumerate(nodes):
+            if m in (i, j, k):
+                continue
+            touched = [x] + [s for s in x.src[:2] if s is not None]
+            if any(_overlaps(s, tn) or _overlaps(s, h) for s in touched):
+                ok = False  # another node reads or writes an intermediate
+            if i < m < k and (_overlaps(x, g) or _overlaps(x, u)):
+                ok = False  # g or u is overwritten before the fused node would read it
+        if ok:
+            return i, j, g, u
+    return None
 
 
 def writeBackMask(nodes, wholeGraph: bool = False) -> list:
@@ -130,7 +199,8 @@ class GGMLHipBackend:
 
     supportsOp is true exactly for the node types lk_hip computes:
     MUL_MAT with src0 in {Q4_0, Q4_1, Q8_0, Q2_K, Q4_K, Q8_K} x src1 F32 -> F32, plus the general
-    F32 x F32 -> F32 and F16 x F16 -> F16 fallbacks. Everything else stays on the CPU
+    F32 x F32 -> F32 and F16 x F16 -> F16 fallbacks, and the F32 element-wise nodes ADD, MUL, GELU
+    and SILU (not on a backend with shardDevices). Everything else stays on the CPU
     backend (GGMLBackendManager's AUTO selection, core/GGMLBackendUtils.kt:152-173).
 
     Host (ByteArray) allocators: the weights of a graph are mirrored in HBM once per weight
@@ -205,6 +275,12 @@ class GGMLHipBackend:
         return isinstance(bufferType, GGMLHipBufferType)
 
     def supportsOp(self, tensor: GGMLTensor) -> bool:
+        if tensor.op in _ELEMENTWISE:
+            # F32 element-wise nodes (the MLP's glue); a sharded backend stays MUL_MAT-only
+            if self.comms:
+                return False
+            srcs = tensor.src[:1] if tensor.op in _UNARY else tensor.src[:2]
+            return tensor.type == GGMLType.F32 and all(s is not None and s.type == GGMLType.F32 for s in srcs)
         if tensor.op != GGMLOp.MUL_MAT:
             return False
         a, b = tensor.src[0], tensor.src[1]
@@ -241,7 +317,9 @@ class GGMLHipBackend:
         written back per writeBackMask, levels of independent nodes grouped into one launch
         each, the device part replayed as a HIP graph; with shardDevices, the graph is
         row-sharded over those GPUs with an RCCL all-gather per level (lk_graph_create_sharded).
-        Device allocators: mutually independent nodes run as one plan, otherwise in order."""
+        Device allocators: mutually independent MUL_MAT nodes run as one plan, otherwise the nodes
+        run in order through the per-op calls (_computeOpsInOrder when the graph holds F32
+        element-wise nodes: ADD, MUL, GELU, SILU)."""
         ga = graph.allocator or self.graphAllocator
         try:
             nodes = [n for n in graph.nodes[: graph.nNodes] if n is not None and n.op != GGMLOp.NONE]
@@ -261,8 +339,9 @@ class GGMLHipBackend:
             if _is_host(ga, nodes[0]):
                 mask = writeBackMask(nodes, self.wholeGraphs)
                 key = ("host", self.weightGeneration, id(ga), _graph_key(ga, nodes, mask))
+                ops = [n.op for n in nodes] if any(n.op != GGMLOp.MUL_MAT for n in nodes) else None
                 g = self._cached(key, lambda: ResidentGraph(ga, [(n.src[0], n.src[1], n) for n in nodes], outputs=mask,
-                                                            weightGeneration=self.weightGeneration, comms=self.comms))
+                                                            weightGeneration=self.weightGeneration, comms=self.comms, ops=ops))
                 if len(self._fast) > 4 * self.MAX_CACHED_GRAPHS:
                     self._fast.clear()
                 self._fast[fast] = key
@@ -270,7 +349,9 @@ class GGMLHipBackend:
                 return GGMLStatus.SUCCESS
             ids = {id(n) for n in nodes}
             independent = all(id(s) not in ids for n in nodes for s in n.src[:2] if s is not None)
-            if independent and len(nodes) > 1:
+            if any(n.op != GGMLOp.MUL_MAT for n in nodes):
+                self._computeOpsInOrder(ga, nodes)
+            elif independent and len(nodes) > 1:
                 key = ("device", id(ga), _graph_key(ga, nodes, [0] * len(nodes)))
                 plan = self._cached(key, lambda: MulMatPlan(ga, [(n.src[0], n.src[1], n) for n in nodes]))
                 plan.launch()
@@ -281,6 +362,35 @@ class GGMLHipBackend:
         except Exception as e:  # mirror of the CPU backend's catch-all
             print(f"GGMLHipBackend: Error computing graph: {e}")
             return GGMLStatus.FAILED
+
+
+    def _computeOpsInOrder(self, ga, nodes):
+        """Device allocators, graphs with element-wise nodes: node by node through the per-op calls;
+        MUL_MAT(W, MUL(ACT(g), u)) whose intermediates nothing else reads runs as one
+        computeMatMulGated (the pattern lk_graph_create_ops fuses; here intermediates consumed only
+        inside the graph are skipped when the backend receives whole graphs)."""
+        skip = set()
+        fusedAt = {}
+        if self.wholeGraphs:
+            for k in range(len(nodes)):
+                m = matchGated(nodes, k)
+                if m is not None and m[0] not in skip and m[1] not in skip:
+                    skip.update(m[:2])
+                    fusedAt[k] = m
+        for k, n in enumerate(nodes):
+            if k in skip:
+                continue
+            if k in fusedAt:
+                _, _, g, u = fusedAt[k]
+                computeMatMulGated(ga, ga.context, n.src[0], g, u, Act.GELU, n)
+            elif n.op == GGMLOp.MUL_MAT:
+                computeMatMul(ga, ga.context, n.src[0], n.src[1], n)
+            elif n.op == GGMLOp.ADD:
+                computeAdd(ga, ga.context, n.src[0], n.src[1], n)
+            elif n.op == GGMLOp.MUL:
+                computeMul(ga, ga.context, n.src[0], n.src[1], n)
+            else:  # GELU, and SILU as the reference computes it
+                computeGelu(ga, ga.context, n.src[0], n)
 
 
 class GGMLBackendRegistration:

@@ -14,6 +14,15 @@
       core/GGMLComputeOps.kt:349-629, the direct dot products (not reachable from
       computeMatMul in the reference), every (row, col) in one launch.
 
+  computeAdd / computeMul / computeGelu / computeSilu (graphAllocator, context, a[, b], dst)
+      core/GGMLComputeOps.kt:735, :811, :1581, :2633 for F32 tensors on device buffers, element by
+      element in the Kotlin order. computeSilu is the reference's: its "quick fallback" computes
+      GELU, so a SILU node is GELU here too; the real SiLU is Act.SILU, by name only
+      (computeUnary / computeMatMulGated).
+  computeMatMulGated(graphAllocator, context, a, gate, up, act, dst)
+      dst = a · (act(gate) ⊙ up): the three reference calls computeGelu, computeMul,
+      computeMatMul in one (lk_mul_mat_gated_device), same bits.
+
 Device buffers go through lk_mul_mat_device on the current torch stream (asynchronous,
 no host sync); host buffers through lk_mul_mat (the Kotlin ByteArray drop-in).
 """
@@ -24,7 +33,18 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .tensor import GGMLCGraph, GGMLContext, GGMLGraphAllocator, GGMLTensor, GGMLType, calculateTensorByteSize
+from .tensor import GGMLCGraph, GGMLContext, GGMLGraphAllocator, GGMLOp, GGMLTensor, GGMLType, calculateTensorByteSize
+
+
+class Act:
+    """lk_act (include/lk_hip.h)."""
+    NONE = 0
+    GELU = 1  # computeGelu's tanh form, core/GGMLComputeOps.kt:1588
+    SILU = 2  # x / (1 + exp(-x)); never chosen for a graph node (the reference's SILU node is GELU)
+
+
+# GGMLOp of this mirror -> the reference's GGMLOp ordinal (enum lk_op, include/lk_hip.h)
+LK_OP = {GGMLOp.ADD: 2, GGMLOp.MUL: 5, GGMLOp.GELU: 19, GGMLOp.SILU: 21, GGMLOp.MUL_MAT: 26}
 
 
 def _is_host(ga: GGMLGraphAllocator, t: GGMLTensor) -> bool:
@@ -101,6 +121,69 @@ def computeMatMul(graphAllocator: GGMLGraphAllocator, context: GGMLContext | Non
     _lib.check(st)
 
 
+def _device_only(graphAllocator, tensors):
+    if any(_is_host(graphAllocator, t) for t in tensors):
+        raise _lib.IllegalArgumentException("element-wise and gated ops take device buffers (host graphs: ResidentGraph)")
+
+
+def computeBinary(op: int, graphAllocator: GGMLGraphAllocator, a: GGMLTensor, b: GGMLTensor, dst: GGMLTensor,
+                  stream=None) -> None:
+    """lk_binary_device: op 1 = ADD, 2 = MUL."""
+    _device_only(graphAllocator, (a, b, dst))
+    L = _lib.load()
+    la, lb, ld = to_lk(graphAllocator, a), to_lk(graphAllocator, b), to_lk(graphAllocator, dst)
+    with _OnStream(stream) as sh:
+        st = L.lk_binary_device(int(op), ctypes.byref(la), ctypes.byref(lb), ctypes.byref(ld), sh)
+    _lib.check(st)
+
+
+def computeUnary(act: int, graphAllocator: GGMLGraphAllocator, a: GGMLTensor, dst: GGMLTensor, stream=None) -> None:
+    """lk_unary_device: dst = act(a), act an Act value."""
+    _device_only(graphAllocator, (a, dst))
+    L = _lib.load()
+    la, ld = to_lk(graphAllocator, a), to_lk(graphAllocator, dst)
+    with _OnStream(stream) as sh:
+        st = L.lk_unary_device(int(act), ctypes.byref(la), ctypes.byref(ld), sh)
+    _lib.check(st)
+
+
+def computeAdd(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor, b: GGMLTensor,
+               dst: GGMLTensor, stream=None) -> None:
+    """core/GGMLComputeOps.kt:735 for F32 (dst may be exactly a or b)."""
+    computeBinary(1, graphAllocator, a, b, dst, stream)
+
+
+def computeMul(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor, b: GGMLTensor,
+               dst: GGMLTensor, stream=None) -> None:
+    """core/GGMLComputeOps.kt:811 for F32."""
+    computeBinary(2, graphAllocator, a, b, dst, stream)
+
+
+def computeGelu(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor, dst: GGMLTensor,
+                stream=None) -> None:
+    """core/GGMLComputeOps.kt:1581 for F32."""
+    computeUnary(Act.GELU, graphAllocator, a, dst, stream)
+
+
+def computeSilu(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor, dst: GGMLTensor,
+                stream=None) -> None:
+    """core/GGMLComputeOps.kt:2633-2638: the reference's SILU node calls computeGelu ("quick fallback
+    using GELU for now"), and so does this. The real SiLU is computeUnary(Act.SILU, ...)."""
+    computeUnary(Act.GELU, graphAllocator, a, dst, stream)
+
+
+def computeMatMulGated(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor, gate: GGMLTensor,
+                       up: GGMLTensor, act: int, dst: GGMLTensor, stream=None) -> None:
+    """dst = a · (act(gate) ⊙ up) (lk_mul_mat_gated_device): computeGelu(gate) -> t, computeMul(t, up) -> h,
+    computeMatMul(a, h, dst) without t and h reaching memory where a streams; same bits either way."""
+    _device_only(graphAllocator, (a, gate, up, dst))
+    L = _lib.load()
+    la, lg, lu, ld = (to_lk(graphAllocator, t) for t in (a, gate, up, dst))
+    with _OnStream(stream) as sh:
+        st = L.lk_mul_mat_gated_device(ctypes.byref(la), ctypes.byref(lg), ctypes.byref(lu), int(act), ctypes.byref(ld), sh)
+    _lib.check(st)
+
+
 def computeMatMulSharded(graphAllocator: GGMLGraphAllocator, context: GGMLContext | None, a: GGMLTensor,
                          b: GGMLTensor, dst: GGMLTensor, nShards: int, firstDevice: int = 0) -> None:
     """computeMatMul over host buffers with A's rows split over nShards GPUs of this process
@@ -129,24 +212,38 @@ class MulMatPlan:
         """stages: None — the nodes are mutually independent (lk_plan_create); or one stage id
         per node (0, non-decreasing) — a chain of dependent stages in one persistent launch with
         a device-side grid barrier between stages (lk_plan_create_chain): stage s+1 may read
-        what stage s wrote."""
+        what stage s wrote.
+
+        A node is (a, b, dst), or (a, gate, dst, up, act) for a gated node a · (act(gate) ⊙ up)
+        (lk_plan_create_gated); in a chain its gate and up may come from the stage before."""
         L = _lib.load()
         n = len(nodes)
         A = (_lib.LkTensor * max(n, 1))()
         B = (_lib.LkTensor * max(n, 1))()
         D = (_lib.LkTensor * max(n, 1))()
-        for i, (a, b, d) in enumerate(nodes):
+        U = (_lib.LkTensor * max(n, 1))()
+        acts = [0] * max(n, 1)
+        for i, node in enumerate(nodes):
+            a, b, d = node[:3]
             A[i], B[i], D[i] = to_lk(ga, a), to_lk(ga, b), to_lk(ga, d)
+            if len(node) == 5:
+                U[i], acts[i] = to_lk(ga, node[3]), int(node[4])
+            elif len(node) != 3:
+                raise _lib.IllegalArgumentException("a node is (a, b, dst) or (a, gate, dst, up, act)")
         self._handle = ctypes.c_void_p()
-        if stages is None:
-            _lib.check(L.lk_plan_create(A, B, D, n, ctypes.byref(self._handle)))
-            S = None
-        else:
+        S = None
+        if stages is not None:
             if len(stages) != n:
                 raise _lib.IllegalArgumentException("one stage id per node")
             S = (ctypes.c_int32 * max(n, 1))(*[int(v) for v in stages])
+        if any(acts):
+            ACT = (ctypes.c_int32 * max(n, 1))(*acts)
+            _lib.check(L.lk_plan_create_gated(A, B, U, ACT, D, S, n, ctypes.byref(self._handle)))
+        elif stages is None:
+            _lib.check(L.lk_plan_create(A, B, D, n, ctypes.byref(self._handle)))
+        else:
             _lib.check(L.lk_plan_create_chain(A, B, D, S, n, ctypes.byref(self._handle)))
-        self._keep = (A, B, D, S)
+        self._keep = (A, B, D, U, S)
 
     def timedOut(self) -> bool:
         """Chain plans: True if a launch gave up waiting at a barrier (grid not co-resident)."""
@@ -186,21 +283,35 @@ class ResidentGraph:
     ``comms``: row-shard the graph over RCCL communicators (lk_graph_create_sharded): a list
     holding this process's ``sharded.Comm`` (one process per GPU), or every rank's Comm of one
     ``sharded.Comm.init_all`` (one process driving several GPUs). Weight nodes then run their
-    rank's rows on each device and an in-place all-gather per level completes every result."""
+    rank's rows on each device and an in-place all-gather per level completes every result.
 
-    def __init__(self, ga: GGMLGraphAllocator, nodes, outputs=None, weightGeneration: int = 0, comms=None):
+    ``ops``: one GGMLOp per node (MUL_MAT, ADD, MUL, GELU, SILU: lk_graph_create_ops) for graphs
+    that hold F32 element-wise nodes too; a unary node is (a, None, dst). MUL_MAT(W, MUL(ACT(g), u))
+    whose intermediates nothing else touches and ``outputs`` does not want back is fused into one
+    gated node (``numFused``). Not with ``comms``: sharded graphs stay MUL_MAT-only."""
+
+    def __init__(self, ga: GGMLGraphAllocator, nodes, outputs=None, weightGeneration: int = 0, comms=None, ops=None):
         L = _lib.load()
         n = len(nodes)
         A = (_lib.LkTensor * max(n, 1))()
         B = (_lib.LkTensor * max(n, 1))()
         D = (_lib.LkTensor * max(n, 1))()
         for i, (a, b, d) in enumerate(nodes):
-            A[i], B[i], D[i] = to_lk(ga, a), to_lk(ga, b), to_lk(ga, d)
+            A[i], D[i] = to_lk(ga, a), to_lk(ga, d)
+            if b is not None:
+                B[i] = to_lk(ga, b)
         outs = None
         if outputs is not None:
             outs = (ctypes.c_uint8 * max(n, 1))(*[1 if o else 0 for o in outputs])
         self._handle = ctypes.c_void_p()
-        if comms:
+        if ops is not None:
+            if comms:
+                raise _lib.NotOffloadedError("sharded graphs are MUL_MAT-only")
+            if len(ops) != n:
+                raise _lib.IllegalArgumentException("one op per node")
+            OPS = (ctypes.c_int32 * max(n, 1))(*[LK_OP.get(o, -1) for o in ops])
+            _lib.check(L.lk_graph_create_ops(OPS, A, B, D, n, outs, weightGeneration, ctypes.byref(self._handle)))
+        elif comms:
             H = (ctypes.c_void_p * len(comms))(*[c._handle for c in comms])
             _lib.check(L.lk_graph_create_sharded(H, len(comms), A, B, D, n, outs, weightGeneration, ctypes.byref(self._handle)))
         else:
@@ -217,6 +328,11 @@ class ResidentGraph:
     @property
     def numLaunches(self) -> int:
         return _lib.load().lk_graph_num_launches(self._handle)
+
+    @property
+    def numFused(self) -> int:
+        """Gated nodes lk_graph_create_ops' fusion pass made."""
+        return _lib.load().lk_graph_num_fused(self._handle)
 
     @property
     def numSharded(self) -> int:
@@ -419,5 +535,6 @@ def scratchBytes() -> int:
 
 
 __all__ = ["syncTimeouts", "setSyncWaitBound", "syncCountersSum", "debugRoute", "debugScratchEpoch",
-           "debugPokeGemmCounter", "scratchRelease", "scratchBytes", "computeMatMul", "computeMatMulSharded", "ResidentGraph", "weightsPinSharded", "validateMatMul", "MulMatPlan", "dequantizeTensor", "quantizeTensor", "weightsPin",
+           "debugPokeGemmCounter", "scratchRelease", "scratchBytes", "Act", "LK_OP", "computeAdd", "computeMul", "computeGelu",
+           "computeSilu", "computeBinary", "computeUnary", "computeMatMulGated", "computeMatMul", "computeMatMulSharded", "ResidentGraph", "weightsPinSharded", "validateMatMul", "MulMatPlan", "dequantizeTensor", "quantizeTensor", "weightsPin",
            "weightsEvictAll", "weightsEvict", "weightsEvictBuffer", "weightsCachedBytes", "weightsCachedCount", "to_lk", "GGMLCGraph", "calculateTensorByteSize"]

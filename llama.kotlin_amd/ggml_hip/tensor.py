@@ -78,7 +78,12 @@ _BYTE_SIZE = {
 class GGMLOp(enum.Enum):
     NONE = 0
     MUL_MAT = 1
-    ADD = 2  # present so supportsOp has something to refuse
+    ADD = 2
+    # the F32 element-wise nodes the backend takes besides MUL_MAT; values are this mirror's own
+    # (ops.LK_OP maps them to the reference's GGMLOp ordinals the C-ABI uses)
+    MUL = 5
+    GELU = 19
+    SILU = 21
 
 
 def calculateContiguousStrides(ne, type_: GGMLType, rank: int | None = None):

@@ -121,11 +121,12 @@ fun computeDotProductQ80Q80Hip(graphAllocator: GGMLGraphAllocator, a: GGMLTensor
     computeDotProductMatrixHip(graphAllocator, LK_DOT_Q8_0_Q8_0, a, b, commonDimK)[row * b.ne[0].toInt() + col]
 
 /**
- * A GGMLBackend that offloads MUL_MAT to the MI355X and defers everything else to the CPU backend.
+ * A GGMLBackend that offloads MUL_MAT — and, unsharded, the F32 element-wise nodes ADD, MUL, GELU and
+ * SILU between a layer's MUL_MATs — to the MI355X and defers everything else to the CPU backend.
  *
  * graphCompute (K/core/GGMLCpuBackend.kt:167-176 contract) walks the graph in node order
  * (computeGraph, K/core/GGMLComputeOps.kt:2515-2523) and cuts it into runs of consecutive
- * offloadable MUL_MAT nodes. Each run is one lk_graph (include/lk_hip.h), created once and cached
+ * offloadable nodes. Each run is one lk_graph (include/lk_hip.h), created once and cached
  * by the run's full tensor descriptors and the weight generation: weights stay mirrored in HBM,
  * independent nodes of a dependency level share one launch, and the device part is replayed as a
  * HIP graph. Every result reaches the ByteArrays by default: the graph may be one split of a larger
@@ -228,7 +229,26 @@ class GGMLHipBackend(private val device: Int = 0, private val shards: Int = 1,
         runs.clear()
     }
 
+    /** GGMLOp -> lk_op (include/lk_hip.h): the enum's ordinal for the nodes an lk_graph takes. */
+    private fun lkOp(op: GGMLOp): Int = when (op) {
+        GGMLOp.ADD -> LK_OP_ADD.toInt()
+        GGMLOp.MUL -> LK_OP_MUL.toInt()
+        GGMLOp.GELU -> LK_OP_GELU.toInt()
+        GGMLOp.SILU -> LK_OP_SILU.toInt()  // computed as GELU, as computeSilu does (K/core/GGMLComputeOps.kt:2633-2638)
+        else -> LK_OP_MUL_MAT.toInt()
+    }
+
+    private fun isUnary(op: GGMLOp) = op == GGMLOp.GELU || op == GGMLOp.SILU
+
     override fun supportsOp(tensor: GGMLTensor): Boolean {
+        if (tensor.op == GGMLOp.ADD || tensor.op == GGMLOp.MUL || isUnary(tensor.op)) {
+            // the F32 element-wise nodes between a layer's MUL_MATs (lk_graph_create_ops); sharded
+            // backends stay MUL_MAT-only
+            if (shards > 1) return false
+            val a = tensor.src[0] ?: return false
+            val bOk = isUnary(tensor.op) || tensor.src[1]?.type == GGMLType.F32
+            return a.type == GGMLType.F32 && bOk && tensor.type == GGMLType.F32
+        }
         if (tensor.op != GGMLOp.MUL_MAT) return false
         val a = tensor.src[0] ?: return false
         val b = tensor.src[1] ?: return false
@@ -289,8 +309,11 @@ class GGMLHipBackend(private val device: Int = 0, private val shards: Int = 1,
         fun buf(t: GGMLTensor): ByteArray? = ga.buffers.getOrNull(t.bufferId)
         val key = ArrayList<Long>(run.size * 3 * 12 + 1)
         key.add(weightGeneration.toLong())
+        val hasOps = run.any { it.op != GGMLOp.MUL_MAT }
         for ((k, n) in run.withIndex()) {
-            for (t in listOf(n.src[0]!!, n.src[1]!!, n)) {
+            key.add(lkOp(n.op).toLong())
+            // a unary node has no src[1]: its own src[0] stands in (lk_graph_create_ops ignores b there)
+            for (t in listOf(n.src[0]!!, n.src[1] ?: n.src[0]!!, n)) {
                 val b = buf(t)
                 bufs.add(b)
                 key.add(lkTypeId(t.type).toLong())
@@ -317,16 +340,21 @@ class GGMLHipBackend(private val device: Int = 0, private val shards: Int = 1,
             val lb = allocArray<lk_tensor>(n)
             val ld = allocArray<lk_tensor>(n)
             val outs = allocArray<UByteVar>(n)
+            val ops = allocArray<IntVar>(n)
             for ((k, node) in run.withIndex()) {
                 val a = node.src[0]!!
-                val b = node.src[1]!!
+                val b = node.src[1] ?: a
+                ops[k] = lkOp(node.op)
                 fill(la[k], a, addr(buf(a)), buf(a)?.size ?: 0)
                 fill(lb[k], b, addr(buf(b)), buf(b)?.size ?: 0)
                 fill(ld[k], node, addr(buf(node)), buf(node)?.size ?: 0)
                 outs[k] = if (writeBack[k]) 1u else 0u
             }
             val h = alloc<CPointerVar<lk_graph>>()
+            // with element-wise nodes in the run: lk_graph_create_ops, which also fuses
+            // MUL_MAT(W, MUL(ACT(g), u)) into one gated node when the write-back mask lets it
             val st = if (comms != null) lk_graph_create_sharded(comms, shards, la, lb, ld, n, outs, weightGeneration, h.ptr)
+                     else if (hasOps) lk_graph_create_ops(ops, la, lb, ld, n, outs, weightGeneration, h.ptr)
                      else lk_graph_create(la, lb, ld, n, outs, weightGeneration, h.ptr)
             if (st != LK_OK.toInt()) {
                 pins.forEach { it.unpin() }
